@@ -44,9 +44,18 @@ Modes and legs:
   --box-dist pets     per-detection box sizes from a seeded PETS-like
                       distribution (synth.pets_box_sizes): windows of every
                       kernel class in one frame.
-  At N = 1 the default line also carries `legs`: configs[3] on one GPU,
-  configs[4] on one GPU, the GridFAST Run and the PETS-like mixed-box Run
-  (--no-legs skips them).
+  --dump-outputs DIR  after the timed steps, what the last timed step handed
+                      over as DIR/<name>.npy (float64; dump_tracker_outputs;
+                      the kernel modes: next_xy, err, status of every point).
+  --full              everything beside the headline figure: the per-launch
+                      HIP-event timing after the timed region (--measure-steps)
+                      and the isolated launches behind `roofline`, the CPU
+                      baselines, `secondary`, and at N = 1 the `legs`:
+                      configs[3] on one GPU, configs[4] on one GPU, the GridFAST
+                      Run and the PETS-like mixed-box Run (--no-legs,
+                      --no-secondary, --no-cpu-baseline, --no-isolated skip
+                      parts of it). A plain run sets up, warms up, times the
+                      steps and prints the line.
 
 Multi-GPU: `python bench.py --gpus N` starts N ranks itself (one process per
 GPU, RANK/LOCAL_RANK/WORLD_SIZE set before anything touches a GPU); under
@@ -474,6 +483,8 @@ def tracker_run(args, world=1, rank=0, local_rank=0, steps=None, warmup=None):
     barrier(world)
     elapsed = time.perf_counter() - t0
     elapsed = pdist.max_over_ranks(elapsed)
+    # the last timed frame's hand-off (the frames after it reuse the buffers)
+    timed_last = np.array(gathered, copy=True).reshape(-1, slot_bytes) if rank == 0 and args.dump_outputs else None
     if parts is not None:
         for p_ in parts:
             if sum(p_[1:4]) > 4.0:
@@ -521,10 +532,45 @@ def tracker_run(args, world=1, rank=0, local_rank=0, steps=None, warmup=None):
             "measure_steps": measure,
             "per_kernel": per_kernel, "ts": ts, "samples": samples, "objs_last": objs_last,
             "points_per_camera": pts_last, "recorded": recorded, "slot_bytes": slot_bytes, "max_obj": max_obj,
+            "timed_last": timed_last,
             "setup": {"group_create_ms": round(create_ms, 3),
                       "sdma_warmup_ms": None if warm_ms is None else round(warm_ms, 3),
                       "note": "outside the timed region: psn_t2d_group creation, of which the process's first "
                               "psn_lk_create sets up every SDMA engine (psn_lk_sdma_warmup_ms)"}}
+
+
+def save_outputs(dirpath, arrays):
+    """--dump-outputs: every array as dirpath/<name>.npy (float64 holds every
+    field exactly: ids and frame indices are 32-bit, coordinates float32)."""
+    os.makedirs(dirpath, exist_ok=True)
+    total = sum(a.size * 8 for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(a, np.float64))
+
+
+def dump_tracker_outputs(dirpath, r):
+    """What the last timed step handed over (every camera's packed
+    stTrack2DResult, unpacked as Associator3D would):
+      objects.npy      one row per reported object, cameras in slot order:
+                       cam_id, frame_idx, id, box x y w h, head x y w h, score,
+                       number of featurePointsPrev, of featurePointsCurr
+      points_prev.npy  cam_id, object id, x, y of every featurePointsPrev entry
+      points_curr.npy  the same of featurePointsCurr"""
+    from mcmtt_opticalflow_amd import tracker2d as t2d
+
+    objs, prev, curr = [], [], []
+    for row in r["timed_last"]:
+        res = t2d.unpack_result(row, r["max_obj"], 1)
+        for o in res["objects"]:
+            objs.append([res["cam_id"], res["frame_idx"], o["id"], *o["box"], *o["head"], o["score"],
+                         len(o["prev"]), len(o["curr"])])
+            for dst, pts in ((prev, o["prev"]), (curr, o["curr"])):
+                p = np.asarray(pts, np.float64).reshape(-1, 2)
+                dst.append(np.column_stack([np.full(len(p), res["cam_id"]), np.full(len(p), o["id"]), p]))
+    save_outputs(dirpath, {"objects": np.asarray(objs, np.float64).reshape(-1, 14),
+                           "points_prev": np.concatenate(prev) if prev else np.zeros((0, 4)),
+                           "points_curr": np.concatenate(curr) if curr else np.zeros((0, 4))})
 
 
 def verify_tracker(args, r):
@@ -959,7 +1005,8 @@ def tracker_line(args, r, world, C, scaling, profile):
                         "bytes_formula": "SURVEY 8(d) c_in*S0 + 4*S_pyr - S_top + 21*N, c_in = 3 (BGR)",
                         "achieved_GBps_per_gpu": round(frame_b * per_gpu_fps / 1e9, 3),
                         "hbm_fraction": round(frame_b * per_gpu_fps / 1e9 / HBM_PEAK_GBPS, 6),
-                        "lk_ms_per_step": round(r["ts"]["track_ms"] / max(r["measure_steps"], 1), 4),
+                        "lk_ms_per_step": (round(r["ts"]["track_ms"] / r["measure_steps"], 4)
+                                           if r["measure_steps"] else None),
                         "lk_timing_note": "LK launch times from HIP events in the measure_steps frames after the "
                                           "timed region (no events inside it)"},
         "compute": {"window_samples_per_camera_frame": round(r["samples"] / cam_frames) if r["samples"] else None,
@@ -997,6 +1044,8 @@ def tracker_main(args):
     C = r["cams_per_rank"]
     out = None
     if rank == 0:
+        if args.dump_outputs:
+            dump_tracker_outputs(args.dump_outputs, r)
         out = tracker_line(args, r, world, C, "strong" if args.total_cameras else "weak", profile)
         if args.verify:
             out["verify"] = verify_tracker(args, r)
@@ -1038,7 +1087,7 @@ def run_child(argv, timeout=600):
 
 def child_args(args, **over):
     """argv of a child line: this run's shared options plus the leg's own."""
-    base = ["--no-legs", "--no-secondary", "--no-cpu-baseline", "--no-isolated", "--period", str(args.period),
+    base = ["--full", "--no-legs", "--no-secondary", "--no-cpu-baseline", "--no-isolated", "--period", str(args.period),
             "--measure-steps", str(args.measure_steps), "--profile", args.profile]
     if args.lib_dir:
         base += ["--lib-dir", args.lib_dir]
@@ -1201,7 +1250,7 @@ def kernel_run(args, steps, warmup, world=1, rank=0, local_rank=0, C=1, W=1920, 
     # every step's slot headers (cam, frame, npts, 0), prepared in pinned host
     # memory before the timed region and written by one small copy kernel per
     # step (psn_t2d_upload_device), the frame index of the slot the LK fills
-    measure = max(1, min(steps, 50))
+    measure = max(1, min(steps, 50)) if args.full else 0
     t_end = warmup + steps + measure + 2
     hdr_alloc = pinned_allocator("hip-coherent")
     hdr_pin = hdr_alloc((t_end, C * 16))
@@ -1237,13 +1286,23 @@ def kernel_run(args, steps, warmup, world=1, rank=0, local_rank=0, C=1, W=1920, 
         t += 1
     hip.synchronize()
     elapsed = time.perf_counter() - t0
+    last = None
+    if rank == 0 and args.dump_outputs:  # the last timed step's slot(s): next_xy, err, status of every point
+        buf, nr = (gathered, world) if comm is not None else (slots[(t - 1) % 2], 1)
+        raw = buf.to_array((nr, sb), np.uint8)
+        M = C * N
+        last = {"next_xy": np.concatenate([raw[i, offs[1]:offs[2]].view(np.float32).reshape(M, 2) for i in range(nr)]),
+                "err": np.concatenate([raw[i, offs[2]:offs[3]].view(np.float32) for i in range(nr)]),
+                "status": np.concatenate([raw[i, offs[3]:offs[3] + M] for i in range(nr)])}
     # launch durations after the timed region (HIP events on the LK stream)
-    ctx.enable_timing(measure + 1, 1)
-    for _ in range(measure):
-        step(t)
-        t += 1
-    hip.synchronize()
-    ts = ctx.timing_stats()
+    ts = {"track_ms": 0.0, "n_track": 0}
+    if measure:
+        ctx.enable_timing(measure + 1, 1)
+        for _ in range(measure):
+            step(t)
+            t += 1
+        hip.synchronize()
+        ts = ctx.timing_stats()
     ctx.close()
     if smoother is not None:
         smoother.close()
@@ -1256,11 +1315,22 @@ def kernel_run(args, steps, warmup, world=1, rank=0, local_rank=0, C=1, W=1920, 
         pinned.close()
     hdr_alloc.close()
     pyr_b, lk_b = algorithmic_bytes(W, H, levels, N)
-    lk_us = 1e3 * ts["track_ms"] / max(ts["n_track"], 1)
+    lk_us = 1e3 * ts["track_ms"] / ts["n_track"] if ts["n_track"] else None  # None: a plain run times no launch
     launch_b = C * lk_b + (pyr_b if mode == 2 else 0)
     return {"fps": C * steps / elapsed, "ms_per_step": 1e3 * elapsed / steps, "lk_us": lk_us,
             "launch_bytes": launch_b, "frame_bytes": pyr_b + lk_b, "scene": scenes[0], "elapsed": elapsed,
-            "mode": mode if ingest == "hbm" else "async-host"}
+            "mode": mode if ingest == "hbm" else "async-host", "last": last}
+
+
+def kernel_roofline(r, kernel, traffic=False):
+    """The kernel modes' roofline from the launch durations measured after the
+    timed region (--full); None without them."""
+    if r["lk_us"] is None:
+        return None
+    ach = r["launch_bytes"] / (r["lk_us"] * 1e-6) / 1e9
+    return {"kernel": kernel, "bound": "latency", "achieved": round(ach, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "frac": round(ach / HBM_PEAK_GBPS, 5), **({"traffic": None} if traffic else {}),
+            "bytes_per_launch": r["launch_bytes"], "avg_launch_us": round(r["lk_us"], 3)}
 
 
 def kernel_secondary(args):
@@ -1289,7 +1359,8 @@ def config4_run(args, world, rank, local_rank, steps, warmup, ingest="host"):
 
     elapsed = pdist.max_over_ranks(r["elapsed"])
     fps_all = total * steps / elapsed
-    ach = r["launch_bytes"] / (r["lk_us"] * 1e-6) / 1e9
+    if rank == 0 and args.dump_outputs:
+        save_outputs(args.dump_outputs, r["last"])
     src = ("BGR in pinned host memory, uploaded every frame (psn_lk_push_frame_async)" if ingest == "host"
            else "gray resident in HBM (no upload)")
     line = {"workload": f"BASELINE.json configs[4]: {total} cameras ({C} per GPU) x 3840x2160 {src}, "
@@ -1297,10 +1368,7 @@ def config4_run(args, world, rank, local_rank, steps, warmup, ingest="host"):
             "ingest": ingest,
             "value": round(fps_all, 2), "unit": "frames/s", "n_gpus": world, "steps": steps,
             "ms_per_step": round(1e3 * elapsed / steps, 5), "scaling": "strong",
-            "roofline": {"kernel": "lk_kernel_st (all cameras in one launch) + sg_insert_kernel", "bound": "latency",
-                         "achieved": round(ach, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(ach / HBM_PEAK_GBPS, 5), "bytes_per_launch": r["launch_bytes"],
-                         "avg_launch_us": round(r["lk_us"], 3)}}
+            "roofline": kernel_roofline(r, "lk_kernel_st (all cameras in one launch) + sg_insert_kernel")}
     return {"line": line, "fps": fps_all, "elapsed": elapsed}
 
 
@@ -1331,17 +1399,16 @@ def kernel_main(args):
     elapsed = pdist.max_over_ranks(r["elapsed"])
     fps_all = world * C * args.steps / elapsed
     if rank == 0:
-        ach = r["launch_bytes"] / (r["lk_us"] * 1e-6) / 1e9
+        if args.dump_outputs:
+            save_outputs(args.dump_outputs, r["last"])
         out = {"metric": METRIC, "value": round(fps_all, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
                "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 5), "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "u8+f32", "data": "synthetic",
                "config": {"workload": f"BASELINE.json configs[1] shape: {C} camera(s) per GPU, 1920x1080 "
                                       f"gray resident in HBM, {args.kpoints} points, 4 levels, 21x21 window",
                           "cameras": world * C, "cameras_per_gpu": C, "parallelism": f"camera-per-GPU x{world}"},
-               "roofline": {"kernel": "lk_kernel_st" + ("+fused_pyramid" if r["mode"] == 2 else ""), "bound": "latency",
-                            "achieved": round(ach, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                            "frac": round(ach / HBM_PEAK_GBPS, 5), "traffic": None,
-                            "bytes_per_launch": r["launch_bytes"], "avg_launch_us": round(r["lk_us"], 3)},
+               "roofline": kernel_roofline(r, "lk_kernel_st" + ("+fused_pyramid" if r["mode"] == 2 else ""),
+                                           traffic=True),
                "cpu_baseline": None}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = kernel_cpu_baseline(r["scene"], args.period, args.kpoints, (21, 21), 3,
@@ -1437,6 +1504,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--no-legs", action="store_true")
     ap.add_argument("--dry-run", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: per-launch timing and isolated launches "
+                         "(roofline), CPU baselines, secondary, legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--lib-dir", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--runtime", choices=["rocm", "torch"], default="rocm", help=argparse.SUPPRESS)
     ap.add_argument("--c4-ingest", choices=["host", "hbm"], default="host",
@@ -1447,6 +1519,9 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.points % args.boxes:
         raise SystemExit("--points must be a multiple of --boxes")
+    if not args.full:  # a plain run: the headline figure alone
+        args.measure_steps, args.isolated = 0, False
+        args.no_cpu_baseline = args.no_secondary = args.no_legs = True
     return args
 
 
