@@ -1059,19 +1059,21 @@ static int launch_group(psn_lk_ctx *c, std::vector<PlannedQuery *> &grp, int cls
             const int max_ept = forced == 512 ? 2 : psn::kStEPTMax;
             if (forced * max_ept >= maxpx) nt = forced;
         }
-        const int ept = nt == 512 ? (maxpx <= 512 ? 1 : 2) : (maxpx <= 2 * nt ? 2 : 4);
-        int threads = nt * 10 + ept;
+        int ept = nt == 512 ? (maxpx <= 512 ? 1 : 2) : (maxpx <= 2 * nt ? 2 : 4);
+        int ow_e = 0, occ = 1;  // lk_kernel_st<nt, ept, ow_e, occ>
         // one-wave iterations (wave 0 iterates, waves 1-3 stage the next level)
         if (c->onewave && !forced && rows_ow <= psn::kOwMaxRows) {
             const int oept = maxpx <= 512 ? 2 : 4;
             int E = rows_ow <= 4 ? 4 : rows_ow <= 7 ? 7 : rows_ow <= 8 ? 8 : 16;
             if (oept == 4 && E < 8) E = 8;
-            threads = 1000 * E + 2560 + oept;
+            nt = 256;
+            ept = oept;
+            ow_e = E;
             lds = lds_ow;
             // more points than two workgroups per CU hold, and LDS for three:
             // the 168-VGPR variant (three per CU; one-camera launches fit at two)
             if (oept == 2 && E <= 8 && lds_ow <= 53 * 1024 && wgs > 2 * c->num_cus) {
-                threads += 200000;
+                occ = 3;
             } else if (c->st_ovl && E > 4) {
                 // two workgroups per CU: the finer levels' A phase beside the
                 // iterations, per query whose overlapped layout fits
@@ -1103,7 +1105,7 @@ static int launch_group(psn_lk_ctx *c, std::vector<PlannedQuery *> &grp, int cls
             builds = true;
         }
         a.poison_lds = c->poison_lds ? lds : 0;
-        HIPCHK(c, psn::launch_lk(a, wgs, threads, lds, true, c->stream));
+        HIPCHK(c, psn::launch_lk_st(a, wgs, nt, ept, ow_e, occ, lds, c->stream));
         return builds ? mark_fused_build(c, fused_slot) : PSN_LK_OK;
     }
     if (cls == kClsBx) {
@@ -1128,7 +1130,7 @@ static int launch_group(psn_lk_ctx *c, std::vector<PlannedQuery *> &grp, int cls
         if (forced == 64 || forced == 128 || forced == 256) threads = forced;
         lds = 0;
         for (int i = 0; i < a.nq; i++) lds = std::max(lds, psn::lk_lds_bytes(a.q[i].win_w, a.q[i].win_h, a.q[i].tile_rows));
-        HIPCHK(c, psn::launch_lk(a, wgs, threads, lds, false, c->stream));
+        HIPCHK(c, psn::launch_lk(a, wgs, threads, lds, c->stream));
         return PSN_LK_OK;
     }
     // large windows: one HBM slot per workgroup, the grid strides over the points

@@ -1,12 +1,21 @@
 // Device helpers shared by the LK kernels of libpsn_lk.so (psn_lk_kernels.hip,
 // psn_lk_large.hip): OpenCV 2.4.6 rounding / border rules, workgroup sums, the
 // LDS staging walkers and the SSE2 chain layouts. Internal, not installed.
+//
+// The scalar steps of LKTrackerInvoker itself -- the structure-tensor solve and
+// its reject test, the per-iteration update, the convergence / oscillation
+// stop, the SSE2-order combination of the chain sums, the err normalisation --
+// are restated in ONE place, psn_lk_solve.h (pinned by oracle/lk_oracle.c:
+// minEig at :725, the D test at :729). The kernels call it; they contain only
+// how the sums are produced and where the window lives.
 #pragma once
 
 #include <float.h>
 #include <limits.h>
 
 #include "psn_lk_kernels.h"
+#include "psn_lk_solve.h"
+#include "psn_lk_stamps.h"
 
 namespace psn {
 
@@ -60,6 +69,9 @@ __device__ __forceinline__ int wave_sum(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31
     return __builtin_amdgcn_readlane(v, 63);
+}
+__device__ __forceinline__ float readlane_f(float v, int lane) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 // Inclusive prefix sum over the 64 lanes (the wave_sum sequence without the final readlane).
 __device__ __forceinline__ int wave_scan(int v) {

@@ -407,10 +407,15 @@ constexpr int kStMaxLds = 150 * 1024;
 // Launchers (psn_lk_kernels.hip).
 hipError_t launch_pyramid(const PyrBuildArgs &a, hipStream_t s);
 void pyramid_grid(const PyrBuildArgs &a, int &tiles_x, int &tiles_y, int &lds_bytes);
-// threads: tiled kernel = workgroup size; single-tile kernel = NT * 10 + EPT,
-// plus 1000 * E for the one-wave iteration mode (E window rows per lane).
-hipError_t launch_lk(const LkLaunchArgs &a, int total_wgs, int threads, int lds_bytes, bool single_tile, hipStream_t s);
-// Box-window kernel with UPT units per thread (4, 8, 10 or 12).
+// Tiled kernel with a workgroup of `threads` (64, 128 or 256).
+hipError_t launch_lk(const LkLaunchArgs &a, int total_wgs, int threads, int lds_bytes, hipStream_t s);
+// Single-tile kernel lk_kernel_st<nt, ept, e, occ>: workgroup size, window pixels
+// per thread, window rows per lane of the one-wave iteration mode (0: multi-wave
+// iterations), workgroups per CU the build is held to (1 or 3). A combination
+// that is not instantiated (PSN_ST_KERNELS, psn_lk_kernels.hip) is hipErrorInvalidValue.
+hipError_t launch_lk_st(const LkLaunchArgs &a, int total_wgs, int nt, int ept, int e, int occ, int lds_bytes,
+                        hipStream_t s);
+// Box-window kernel with UPT units per thread (4, 8, 10, 12 or 16).
 // notail: every query of the launch sums in the SSE2 order with width % 8 == 0
 // (no scalar-tail chain: a build without its per-pixel bookkeeping)
 hipError_t launch_lk_bx(const LkLaunchArgs &a, int total_wgs, int upt, bool notail, int lds_bytes, hipStream_t s);

@@ -30,27 +30,10 @@
 namespace psn {
 
 
-// Diagnostic build (-DPSN_LK_STAMPS): shader-clock stamps of workgroup phases.
-#ifdef PSN_LK_STAMPS
-// ordered: the stamp is taken where it stands in program order (issue time)
-#define LK_STAMP(slot)                                                                            \
-    do {                                                                                          \
-        unsigned long long t_s;                                                                   \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_s) : : "memory");             \
-        if (threadIdx.x == 0 && A.stamps) A.stamps[(size_t)blockIdx.x * 64 + (slot)] = t_s;      \
-    } while (0)
-#define LK_COUNT(slot, v)                                                          \
-    do {                                                                           \
-        if (threadIdx.x == 0 && A.stamps) A.stamps[(size_t)blockIdx.x * 64 + (slot)] = (v); \
-    } while (0)
-#else
-#define LK_STAMP(slot) \
-    do {              \
-    } while (0)
-#define LK_COUNT(slot, v) \
-    do {                 \
-    } while (0)
-#endif
+// Diagnostic build (-DPSN_LK_STAMPS, psn_lk_stamps.h): thread 0's shader clock at
+// workgroup phase `slot` (or a value) into stamps[workgroup][slot].
+#define LK_STAMP(slot) PSN_STAMP(A.stamps, threadIdx.x == 0, (size_t)blockIdx.x * 64 + (slot))
+#define LK_COUNT(slot, v) PSN_STAMP_VAL(A.stamps, threadIdx.x == 0, (size_t)blockIdx.x * 64 + (slot), v)
 
 
 // ---------------------------------------------------------------------------
@@ -294,7 +277,6 @@ __global__ __launch_bounds__(NT) void lk_kernel(LkLaunchArgs A) {
     }
     int status = 1;
     float errv = 0.f;
-    const float FLT_SCALE = 1.f / (1 << 20);
 
     for (int level = maxL; level >= 0; level--) {
         const LevelDev I = A.slots[Q.prev_slot * kMaxLevels + level];
@@ -320,6 +302,8 @@ __global__ __launch_bounds__(NT) void lk_kernel(LkLaunchArgs A) {
         px = __fsub_rn(px, hwx);
         py = __fsub_rn(py, hwy);
         const int ipx = cv_floor(px), ipy = cv_floor(py);
+        // (win_outside, written out at this kernel's three sites: through the helper the
+        // compiler folds the tests differently and lk_kernel<256> changes its VGPR count)
         if (ipx < -w || ipx >= cols || ipy < -h || ipy >= rows) {
             if (level == 0) {
                 status = 0;
@@ -394,7 +378,7 @@ __global__ __launch_bounds__(NT) void lk_kernel(LkLaunchArgs A) {
         __syncthreads();  // Iw / Dw complete
         block_reduce4<NT, true>(sA11, sA12, aA12, sA22, REDI);
         const bool ex11 = sA11 <= kExact, ex12 = aA12 <= (unsigned)kExact, ex22 = sA22 <= (unsigned)kExact;
-        float A11 = (float)sA11, A12 = (float)sA12, A22 = (float)sA22;
+        float r11 = (float)sA11, r12 = (float)sA12, r22 = (float)sA22;  // the raw A sums
         if (!(ex11 && ex12 && ex22)) {
             // ordered float chains over (float)(Ix*Ix), (float)(Ix*Iy), (float)(Iy*Iy)
             float acc = 0.f;
@@ -423,34 +407,18 @@ __global__ __launch_bounds__(NT) void lk_kernel(LkLaunchArgs A) {
             __syncthreads();
             float s3[3];
 #pragma unroll
-            for (int s = 0; s < 3; s++) {
-                float tail = RED[s * 5 + 4];
-                if (sse) {
-                    const float q = __fadd_rn(__fadd_rn(__fadd_rn(RED[s * 5 + 0], RED[s * 5 + 1]), RED[s * 5 + 2]), RED[s * 5 + 3]);
-                    tail = __fadd_rn(tail, q);
-                }
-                s3[s] = tail;
-            }
-            if (!ex11) A11 = s3[0];
-            if (!ex12) A12 = s3[1];
-            if (!ex22) A22 = s3[2];
+            for (int s = 0; s < 3; s++) s3[s] = combine_a5([&](int i) { return RED[i]; }, s, sse);
+            if (!ex11) r11 = s3[0];
+            if (!ex12) r12 = s3[1];
+            if (!ex22) r22 = s3[2];
         }
-        A11 = __fmul_rn(A11, FLT_SCALE);
-        A12 = __fmul_rn(A12, FLT_SCALE);
-        A22 = __fmul_rn(A22, FLT_SCALE);
-        float D = __fsub_rn(__fmul_rn(A11, A22), __fmul_rn(A12, A12));
-        {
-            const float dd = __fsub_rn(A11, A22);
-            const float t = __fadd_rn(__fmul_rn(dd, dd), __fmul_rn(__fmul_rn(4.f, A12), A12));
-            const float minEig = __fdiv_rn(__fsub_rn(__fadd_rn(A22, A11), sqrtf(t)), (float)(2 * w * h));
-            if (flags & PSN_LK_GET_MIN_EIGENVALS) errv = minEig;
-            if (minEig < Q.min_eig || D < FLT_EPSILON) {
-                if (level == 0) status = 0;
-                __syncthreads();
-                continue;
-            }
+        const LkSolve S = lk_solve(r11, r12, r22, w * h, Q.min_eig);
+        if (flags & PSN_LK_GET_MIN_EIGENVALS) errv = S.minEig;
+        if (!S.ok) {
+            if (level == 0) status = 0;
+            __syncthreads();
+            continue;
         }
-        D = __fdiv_rn(1.f, D);
         float pdx = 0.f, pdy = 0.f;
 
         for (int j = 0; j < Q.max_count; j++) {
@@ -460,7 +428,7 @@ __global__ __launch_bounds__(NT) void lk_kernel(LkLaunchArgs A) {
                 break;
             }
             bilin_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny), iw00, iw01, iw10, iw11);
-            if (!(jr_valid && inx >= jr_x0 && iny >= jr_y0 && inx + w + 1 <= jr_x0 + JRW && iny + h + 1 <= jr_y0 + JRH)) {
+            if (!(jr_valid && jr_covers(inx, iny, w, h, jr_x0, jr_y0, JRW, JRH))) {
                 jr_x0 = inx - kJMargin;
                 jr_y0 = iny - kJMargin;
                 jr_valid = true;
@@ -519,36 +487,12 @@ __global__ __launch_bounds__(NT) void lk_kernel(LkLaunchArgs A) {
                 }
                 if (tid < 10) RED[16 + tid] = bacc;
                 __syncthreads();
-                b1 = RED[16 + 4];
-                b2 = RED[16 + 9];
-                if (sse) {
-                    // bbuf = qb0 + qb1; b1 += bbuf[0] + bbuf[2]; b2 += bbuf[1] + bbuf[3]
-                    const float bb0 = __fadd_rn(RED[16 + 0], RED[16 + 2]);
-                    const float bb2 = __fadd_rn(RED[16 + 1], RED[16 + 3]);
-                    const float bb1 = __fadd_rn(RED[16 + 5], RED[16 + 7]);
-                    const float bb3 = __fadd_rn(RED[16 + 6], RED[16 + 8]);
-                    b1 = __fadd_rn(b1, __fadd_rn(bb0, bb2));
-                    b2 = __fadd_rn(b2, __fadd_rn(bb1, bb3));
-                }
+                combine_b10([&](int i) { return RED[16 + i]; }, sse, b1, b2);
                 __syncthreads();  // RED read by all before any later write
             }
-            b1 = __fmul_rn(b1, FLT_SCALE);
-            b2 = __fmul_rn(b2, FLT_SCALE);
-            const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, b2), __fmul_rn(A22, b1)), D);
-            const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, b1), __fmul_rn(A11, b2)), D);
-            nx = __fadd_rn(nx, dx);
-            ny = __fadd_rn(ny, dy);
-            NPx = __fadd_rn(nx, hwx);
-            NPy = __fadd_rn(ny, hwy);
-            const double dd = __dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy));
-            if (dd <= Q.eps2) break;
-            if (j > 0 && (double)fabsf(__fadd_rn(dx, pdx)) < 0.01 && (double)fabsf(__fadd_rn(dy, pdy)) < 0.01) {
-                NPx = __fsub_rn(NPx, __fmul_rn(dx, 0.5f));
-                NPy = __fsub_rn(NPy, __fmul_rn(dy, 0.5f));
-                break;
-            }
-            pdx = dx;
-            pdy = dy;
+            float dx, dy;
+            const double dd = lk_update(S.A11, S.A12, S.A22, S.invD, b1, b2, hwx, hwy, nx, ny, NPx, NPy, dx, dy);
+            if (lk_stop(dd, Q.eps2, j, dx, dy, pdx, pdy, NPx, NPy)) break;
         }
 
         if (level == 0 && status && A.err && (flags & PSN_LK_GET_MIN_EIGENVALS) == 0) {
@@ -560,7 +504,7 @@ __global__ __launch_bounds__(NT) void lk_kernel(LkLaunchArgs A) {
                 continue;
             }
             bilin_weights(__fsub_rn(qx, (float)iqx), __fsub_rn(qy, (float)iqy), iw00, iw01, iw10, iw11);
-            if (!(jr_valid && iqx >= jr_x0 && iqy >= jr_y0 && iqx + w + 1 <= jr_x0 + JRW && iqy + h + 1 <= jr_y0 + JRH)) {
+            if (!(jr_valid && jr_covers(iqx, iqy, w, h, jr_x0, jr_y0, JRW, JRH))) {
                 jr_x0 = iqx - kJMargin;
                 jr_y0 = iqy - kJMargin;
                 jr_valid = true;
@@ -605,7 +549,7 @@ __global__ __launch_bounds__(NT) void lk_kernel(LkLaunchArgs A) {
                 __syncthreads();
                 errval = RED[32];
             }
-            errv = __fdiv_rn(__fmul_rn(errval, 1.f), (float)(32 * w * h));
+            errv = lk_err(errval, w * h);
         }
         __syncthreads();  // LDS reuse by the next level
     }
@@ -654,10 +598,6 @@ __device__ __forceinline__ float chain_sum16(const float *p, int nb) {
         a3 = c3;
     }
     return add16(acc, a0, a1, a2, a3);
-}
-
-__device__ __forceinline__ float readlane_f(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
 // Chain-major geometry of a w x h window, regions padded to 16 floats.
@@ -988,7 +928,7 @@ __device__ __forceinline__ IGeo i_geo(float px0, float py0, float hwx, float hwy
     const float px = __fsub_rn(__fmul_rn(px0, scale), hwx), py = __fsub_rn(__fmul_rn(py0, scale), hwy);
     gg.ipx = cv_floor(px);
     gg.ipy = cv_floor(py);
-    gg.valid = !(gg.ipx < -w || gg.ipx >= cols || gg.ipy < -h || gg.ipy >= rows);
+    gg.valid = !win_outside(gg.ipx, gg.ipy, w, h, cols, rows);
     bilin_weights(__fsub_rn(px, (float)gg.ipx), __fsub_rn(py, (float)gg.ipy), gg.w00, gg.w01, gg.w10, gg.w11);
     return gg;
 }
@@ -1022,40 +962,25 @@ __device__ __forceinline__ void pyr_tail(const LkLaunchArgs &A, uint8_t *smem) {
 }
 
 // Solver table of one level from the A sums (a11, a22 saturating, s12 wrapping)
-// and the 15 ordered chain sums c (sum s = 0..2: chains 5s..5s+3 the SSE2 lanes,
+// and the 15 ordered chain sums c[] (sum s = 0..2: chains 5s..5s+3 the SSE2 lanes,
 // 5s+4 the tail; used only when the sum is not exact as an integer):
-// {A11, A12, A22, 1/D, minEig, ok} as LKTrackerInvoker computes them.
-__device__ __forceinline__ void st_level_table(float *lv, unsigned a11, int s12, unsigned a22, float c0, float c1,
-                                               float c2, float c3, float c4, float c5, float c6, float c7, float c8,
-                                               float c9, float c10, float c11, float c12, float c13, float c14,
+// {A11, A12, A22, 1/D, minEig, ok} as LKTrackerInvoker computes them (lk_solve).
+__device__ __forceinline__ void st_level_table(float *lv, unsigned a11, int s12, unsigned a22, const float (&c)[15],
                                                bool sse, int wh, float min_eig) {
     // a sum whose every term and every partial sum (in any order) is an
     // integer <= 2^24 is exact in float: its integer value; otherwise the
     // ordered chains, combined in the SSE2 build's order
-    float s0 = c4, s1 = c9, s2 = c14;
-    if (sse) {
-        s0 = __fadd_rn(s0, __fadd_rn(__fadd_rn(__fadd_rn(c0, c1), c2), c3));
-        s1 = __fadd_rn(s1, __fadd_rn(__fadd_rn(__fadd_rn(c5, c6), c7), c8));
-        s2 = __fadd_rn(s2, __fadd_rn(__fadd_rn(__fadd_rn(c10, c11), c12), c13));
-    }
-    float A11 = a11 <= (unsigned)kExact ? (float)a11 : s0;
-    float A12 = ((a11 + a22) >> 1) <= (unsigned)kExact ? (float)s12 : s1;
-    float A22 = a22 <= (unsigned)kExact ? (float)a22 : s2;
-    const float FLT_SCALE = 1.f / (1 << 20);
-    A11 = __fmul_rn(A11, FLT_SCALE);
-    A12 = __fmul_rn(A12, FLT_SCALE);
-    A22 = __fmul_rn(A22, FLT_SCALE);
-    const float D = __fsub_rn(__fmul_rn(A11, A22), __fmul_rn(A12, A12));
-    const float dd = __fsub_rn(A11, A22);
-    const float t = __fadd_rn(__fmul_rn(dd, dd), __fmul_rn(__fmul_rn(4.f, A12), A12));
-    const float minEig = __fdiv_rn(__fsub_rn(__fadd_rn(A22, A11), sqrtf(t)), (float)(2 * wh));
-    const bool ok = !(minEig < min_eig || D < FLT_EPSILON);
-    lv[0] = A11;
-    lv[1] = A12;
-    lv[2] = A22;
-    lv[3] = ok ? __fdiv_rn(1.f, D) : 0.f;
-    lv[4] = minEig;
-    lv[5] = ok ? 1.f : 0.f;
+    const auto chain = [&](int i) { return c[i]; };
+    const float s0 = combine_a5(chain, 0, sse), s1 = combine_a5(chain, 1, sse), s2 = combine_a5(chain, 2, sse);
+    const LkSolve S = lk_solve(a11 <= (unsigned)kExact ? (float)a11 : s0,
+                               ((a11 + a22) >> 1) <= (unsigned)kExact ? (float)s12 : s1,
+                               a22 <= (unsigned)kExact ? (float)a22 : s2, wh, min_eig);
+    lv[0] = S.A11;
+    lv[1] = S.A12;
+    lv[2] = S.A22;
+    lv[3] = S.ok ? S.invD : 0.f;
+    lv[4] = S.minEig;
+    lv[5] = S.ok ? 1.f : 0.f;
 }
 
 // Diagnostic stamps of the single-tile kernel (PSN_LK_STAMPS): 60 start, 50
@@ -1135,10 +1060,8 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
         NPx = A.next[2 * pi];
         NPy = A.next[2 * pi + 1];
     }
-#ifdef PSN_LK_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // point landed
+    PSN_STAMPS_ONLY(asm volatile("s_waitcnt vmcnt(0)" ::: "memory");)  // point landed
     LK_STAMP(58);
-#endif
 
     // ---- the I patch of every level by LDS-DMA; the coarsest J region into registers ----
 #pragma unroll
@@ -1299,9 +1222,10 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                 s12 += ra[8];
                 a22 = sat_add(a22, (unsigned)ra[16]);
             }
-            const float *c = CH + l * 15;
-            st_level_table(LV + l * kStLvFloats, a11, s12, a22, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8],
-                           c[9], c[10], c[11], c[12], c[13], c[14], sse, wh, Q.min_eig);
+            float c[15];
+#pragma unroll
+            for (int k = 0; k < 15; k++) c[k] = CH[l * 15 + k];
+            st_level_table(LV + l * kStLvFloats, a11, s12, a22, c, sse, wh, Q.min_eig);
         }
     }
     __syncthreads();  // LV published; the A planes in R are dead from here
@@ -1310,31 +1234,8 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
 
     int status = 1;
     float errv = 0.f;
-    const float FLT_SCALE = 1.f / (1 << 20);
-#ifdef PSN_LK_STAMPS
-    unsigned long long acc_ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_ph = 0;
-// ordered stamps: every earlier instruction has issued and every LDS access landed
-#define PH_STAMP(t) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory")
-#define PH_BEGIN() PH_STAMP(t_ph)
-#define PH_MARK(i)                                                  \
-    do {                                                            \
-        unsigned long long t_;                                      \
-        PH_STAMP(t_);                                               \
-        acc_ph[i] += t_ - t_ph;                                     \
-        t_ph = t_;                                                  \
-    } while (0)
-#define PH_COUNT(i) acc_ph[i]++
-#else
-#define PH_BEGIN() \
-    do {           \
-    } while (0)
-#define PH_MARK(i) \
-    do {           \
-    } while (0)
-#define PH_COUNT(i) \
-    do {            \
-    } while (0)
-#endif
+    // accumulated iteration phases (slots 40..47), ordered stamps
+    PSN_STAMPS_ONLY(unsigned long long acc_ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_ph = 0;)
     int jr_x0 = 0, jr_y0 = 0;
 
     if constexpr (E > 0) {
@@ -1456,8 +1357,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
 #pragma unroll
             for (int k = 0; k < 15; k++) c[k] = readlane_f(acc, k);
             if (lane == 0)
-                st_level_table(LV + l * kStLvFloats, s11, s12, s22, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7],
-                               c[8], c[9], c[10], c[11], c[12], c[13], c[14], sse, wh, Q.min_eig);
+                st_level_table(LV + l * kStLvFloats, s11, s12, s22, c, sse, wh, Q.min_eig);
         };
         LK_STAMP(54);
         bool pf_regs = true;  // the prefetched region is still in registers (prologue) vs already in LDS
@@ -1503,8 +1403,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
             if (run) {
                 const int inx0 = __builtin_amdgcn_readfirstlane(cv_floor(nx));
                 const int iny0 = __builtin_amdgcn_readfirstlane(cv_floor(ny));
-                if (pf_level == level && inx0 >= pf_x0 && iny0 >= pf_y0 && inx0 + w + 1 <= pf_x0 + JRW &&
-                    iny0 + h + 1 <= pf_y0 + JRH) {
+                if (pf_level == level && jr_covers(inx0, iny0, w, h, pf_x0, pf_y0, JRW, JRH)) {
                     if (pf_regs) {
                         LK_STAMP(55);
                         pf.store(JC);
@@ -1531,11 +1430,8 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
             if (wid != 0) {
                 if (ovl && level == maxL) {  // the finer levels' A phase: wave k takes levels maxL - k, maxL - k - 3, ...
                     for (int l = maxL - wid; l >= 0; l -= NW - 1) a_level_wave(l);
-#ifdef PSN_LK_STAMPS
-                    unsigned long long t_s;  // wave k's A phase done: slot 59 - 10 k
-                    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_s) : : "memory");
-                    if (lane == 0 && wid < 4 && A.stamps) A.stamps[(size_t)blockIdx.x * 64 + 59 - 10 * wid] = t_s;
-#endif
+                    // wave k's A phase done: slot 59 - 10 k
+                    PSN_STAMP(A.stamps, lane == 0 && wid < 4, (size_t)blockIdx.x * 64 + 59 - 10 * wid);
                 }
                 if (level > 0) {
                     JPStage<NT> cp;
@@ -1606,7 +1502,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                 };
                 for (int j = 0; j < maxc; j++) {
                     jdone = j + 1;
-                    PH_BEGIN();
+                    PSN_CLK_ORDERED(t_ph);
                     const int inx = cv_floor(nx), iny = cv_floor(ny);
                     int iw00, iw01, iw10, iw11;
                     bilin_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny), iw00, iw01, iw10, iw11);
@@ -1621,11 +1517,12 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                     // keep the (rarely taken) branches below the products: the
                     // conditions formally depend on them
                     asm volatile("; order %2 %3 %4 %5" : "+s"(sinx), "+s"(siny) : "v"(s1), "v"(s2), "v"(a), "v"(a2));
+                    // (win_outside, written out: through the helper the one-wave builds' VGPR counts move)
                     if (sinx < -w || sinx >= cols || siny < -h || siny >= rows) {
                         if (level == 0) status = 0;
                         break;
                     }
-                    if (!(sinx >= jr_x0 && siny >= jr_y0 && sinx + w + 1 <= jr_x0 + JRW && siny + h + 1 <= jr_y0 + JRH)) {
+                    if (!(jr_covers(sinx, siny, w, h, jr_x0, jr_y0, JRW, JRH))) {
                         // restage by this wave alone (the other waves never read JC)
                         JPStage<NT> cp;
                         cp.cs = JRHc;
@@ -1635,20 +1532,20 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                         cp.copy(JC, J, jr_y0, jr_x0, JRW, JRH, wk0_int, wk0_bord);
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                         products(sinx - jr_x0, siny - jr_y0, W0, W1, s1, s2, a, a2);
-                        PH_COUNT(5);
+                        PSN_PH_COUNT(acc_ph, 5);
                     }
-                    PH_MARK(0);
+                    PSN_PH_MARK(acc_ph, t_ph, 0);
                     const int l1 = s1, l2 = s2;  // the lane's own sums (class path)
                     const unsigned la1 = a, la2 = a2;
                     wave_sum4(s1, s2, a, a2);
-                    PH_MARK(1);
+                    PSN_PH_MARK(acc_ph, t_ph, 1);
                     float b1, b2;
                     if (sums_exact(a, s1) && sums_exact(a2, s2)) {
                         // every partial sum in any order is an integer of magnitude <= 2^24
                         b1 = (float)s1;
                         b2 = (float)s2;
                     } else {
-                        PH_COUNT(6);
+                        PSN_PH_COUNT(acc_ph, 6);
                         // per SSE2 chain class: inclusive scans of the lanes' sums and
                         // of sum|t1|, sum|t2|; class-end lanes publish to LDS
                         unsigned a1 = min(la1, (1u << 25) + 1u);  // a clamped lane fails its class
@@ -1673,14 +1570,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                         if (exact) {
                             // every chain's partial sums are integers <= 2^24: each chain
                             // sum is its integer sum; combine in the SSE2 build's order
-                            b1 = (float)S1[4];
-                            b2 = (float)S2[4];
-                            if (sse) {
-                                b1 = __fadd_rn(b1, __fadd_rn(__fadd_rn((float)S1[0], (float)S1[2]),
-                                                             __fadd_rn((float)S1[1], (float)S1[3])));
-                                b2 = __fadd_rn(b2, __fadd_rn(__fadd_rn((float)S2[0], (float)S2[2]),
-                                                             __fadd_rn((float)S2[1], (float)S2[3])));
-                            }
+                            combine_b10([&](int i) { return (float)(i < 5 ? S1[i] : S2[i - 5]); }, sse, b1, b2);
                         } else {
                             // ordered float chains: products chain-major into R, one lane per chain
 #pragma unroll
@@ -1703,39 +1593,16 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                                 const int nb = (ch < 4 ? GB.S : GB.T) >> 4;
                                 acc = chain_sum16(R + base, nb);
                             }
-                            b1 = readlane_f(acc, 4);
-                            b2 = readlane_f(acc, 9);
-                            if (sse) {
-                                const float bb0 = __fadd_rn(readlane_f(acc, 0), readlane_f(acc, 2));
-                                const float bb2 = __fadd_rn(readlane_f(acc, 1), readlane_f(acc, 3));
-                                const float bb1 = __fadd_rn(readlane_f(acc, 5), readlane_f(acc, 7));
-                                const float bb3 = __fadd_rn(readlane_f(acc, 6), readlane_f(acc, 8));
-                                b1 = __fadd_rn(b1, __fadd_rn(bb0, bb2));
-                                b2 = __fadd_rn(b2, __fadd_rn(bb1, bb3));
-                            }
-                            PH_COUNT(4);
+                            combine_b10([&](int i) { return readlane_f(acc, i); }, sse, b1, b2);
+                            PSN_PH_COUNT(acc_ph, 4);
                         }
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // CSX / R reads done before the next writes
                     }
-                    PH_MARK(2);
-                    b1 = __fmul_rn(b1, FLT_SCALE);
-                    b2 = __fmul_rn(b2, FLT_SCALE);
-                    const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, b2), __fmul_rn(A22, b1)), D);
-                    const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, b1), __fmul_rn(A11, b2)), D);
-                    nx = __fadd_rn(nx, dx);
-                    ny = __fadd_rn(ny, dy);
-                    NPx = __fadd_rn(nx, hwx);
-                    NPy = __fadd_rn(ny, hwy);
-                    const double dd = __dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy));
-                    PH_MARK(3);
-                    if (dd <= eps2) break;
-                    if (j > 0 && (double)fabsf(__fadd_rn(dx, pdx)) < 0.01 && (double)fabsf(__fadd_rn(dy, pdy)) < 0.01) {
-                        NPx = __fsub_rn(NPx, __fmul_rn(dx, 0.5f));
-                        NPy = __fsub_rn(NPy, __fmul_rn(dy, 0.5f));
-                        break;
-                    }
-                    pdx = dx;
-                    pdy = dy;
+                    PSN_PH_MARK(acc_ph, t_ph, 2);
+                    float dx, dy;
+                    const double dd = lk_update(A11, A12, A22, D, b1, b2, hwx, hwy, nx, ny, NPx, NPy, dx, dy);
+                    PSN_PH_MARK(acc_ph, t_ph, 3);
+                    if (lk_stop(dd, eps2, j, dx, dy, pdx, pdy, NPx, NPy)) break;
                 }
                 LK_STAMP(level * 10 + 7);
                 LK_COUNT(level * 10 + 8, jdone);
@@ -1744,12 +1611,12 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                 if (level == 0 && status && A.err && (flags & PSN_LK_GET_MIN_EIGENVALS) == 0) {
                     const float qx = __fsub_rn(NPx, hwx), qy = __fsub_rn(NPy, hwy);
                     const int iqx = cv_floor(qx), iqy = cv_floor(qy);
-                    if (iqx < -w || iqx >= cols || iqy < -h || iqy >= rows) {
+                    if (win_outside(iqx, iqy, w, h, cols, rows)) {
                         status = 0;
                     } else {
                         int iw00, iw01, iw10, iw11;
                         bilin_weights(__fsub_rn(qx, (float)iqx), __fsub_rn(qy, (float)iqy), iw00, iw01, iw10, iw11);
-                        if (!(iqx >= jr_x0 && iqy >= jr_y0 && iqx + w + 1 <= jr_x0 + JRW && iqy + h + 1 <= jr_y0 + JRH)) {
+                        if (!(jr_covers(iqx, iqy, w, h, jr_x0, jr_y0, JRW, JRH))) {
                             JPStage<NT> cp;
                             cp.cs = JRHc;
                             jr_x0 = (iqx - kStJMargin) & ~3;
@@ -1785,7 +1652,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                             if (lane == 0) acc = chain_sum16(R, round16i(wh) >> 4);
                             errval = readlane_f(acc, 0);
                         }
-                        errv = __fdiv_rn(__fmul_rn(errval, 1.f), (float)(32 * wh));
+                        errv = lk_err(errval, wh);
                     }
                 }
             }
@@ -1837,8 +1704,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
         if (run) {
             // this level's J region: the prefetched registers if they cover the start
             const int inx0 = cv_floor(nx), iny0 = cv_floor(ny);
-            if (pf_level == level && inx0 >= pf_x0 && iny0 >= pf_y0 && inx0 + w + 1 <= pf_x0 + JRW &&
-                iny0 + h + 1 <= pf_y0 + JRH) {
+            if (pf_level == level && jr_covers(inx0, iny0, w, h, pf_x0, pf_y0, JRW, JRH)) {
                 pf.store(JP);
                 jr_x0 = pf_x0;
                 jr_y0 = pf_y0;
@@ -1880,15 +1746,15 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
 
         for (int j = 0; j < Q.max_count; j++) {
             jdone = j + 1;
-            PH_BEGIN();
+            PSN_CLK_ORDERED(t_ph);
             const int inx = cv_floor(nx), iny = cv_floor(ny);
-            if (inx < -w || inx >= cols || iny < -h || iny >= rows) {
+            if (win_outside(inx, iny, w, h, cols, rows)) {
                 if (level == 0) status = 0;
                 break;
             }
             int iw00, iw01, iw10, iw11;
             bilin_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny), iw00, iw01, iw10, iw11);
-            if (!(inx >= jr_x0 && iny >= jr_y0 && inx + w + 1 <= jr_x0 + JRW && iny + h + 1 <= jr_y0 + JRH)) {
+            if (!(jr_covers(inx, iny, w, h, jr_x0, jr_y0, JRW, JRH))) {
                 // every wave's JP reads of iteration j-1 precede that iteration's
                 // barrier, which this wave has passed
                 JPStage<NT> cp;
@@ -1896,7 +1762,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                 jr_y0 = iny - kStJMargin;
                 cp.copy(JP, J, jr_y0, jr_x0, JRW, JRH, wk_int, wk_bord);
                 __syncthreads();
-                PH_COUNT(5);
+                PSN_PH_COUNT(acc_ph, 5);
             }
             const unsigned W0 = pack_w(iw00, iw01), W1 = pack_w(iw10, iw11);
             const uint32_t *jb = JP + (iny - jr_y0) * JRW + (inx - jr_x0);
@@ -1915,9 +1781,9 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                 s2 += t2;
                 a += (unsigned)__mul24(abs(diff), (int)Sxy[k]);  // |t1| + |t2| (both factors < 2^14); per thread < 2^30
             }
-            PH_MARK(0);
+            PSN_PH_MARK(acc_ph, t_ph, 0);
             block_sums3<NT>(s1, s2, a, RI + kStRiIt + 32 * (j & 1));  // the iteration's barrier
-            PH_MARK(1);
+            PSN_PH_MARK(acc_ph, t_ph, 1);
             float b1, b2;
             if (a <= (unsigned)kExact) {
                 b1 = (float)s1;
@@ -1930,38 +1796,14 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                     const int nb = (ch < 4 ? GB.S : GB.T) >> 4;
                     acc = chain_sum16(pb + base, nb);
                 }
-                b1 = readlane_f(acc, 4);
-                b2 = readlane_f(acc, 9);
-                if (sse) {
-                    // bbuf = qb0 + qb1; b1 += bbuf[0] + bbuf[2]; b2 += bbuf[1] + bbuf[3]
-                    const float bb0 = __fadd_rn(readlane_f(acc, 0), readlane_f(acc, 2));
-                    const float bb2 = __fadd_rn(readlane_f(acc, 1), readlane_f(acc, 3));
-                    const float bb1 = __fadd_rn(readlane_f(acc, 5), readlane_f(acc, 7));
-                    const float bb3 = __fadd_rn(readlane_f(acc, 6), readlane_f(acc, 8));
-                    b1 = __fadd_rn(b1, __fadd_rn(bb0, bb2));
-                    b2 = __fadd_rn(b2, __fadd_rn(bb1, bb3));
-                }
-                PH_COUNT(4);
+                combine_b10([&](int i) { return readlane_f(acc, i); }, sse, b1, b2);
+                PSN_PH_COUNT(acc_ph, 4);
             }
-            PH_MARK(2);
-            b1 = __fmul_rn(b1, FLT_SCALE);
-            b2 = __fmul_rn(b2, FLT_SCALE);
-            const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, b2), __fmul_rn(A22, b1)), D);
-            const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, b1), __fmul_rn(A11, b2)), D);
-            nx = __fadd_rn(nx, dx);
-            ny = __fadd_rn(ny, dy);
-            NPx = __fadd_rn(nx, hwx);
-            NPy = __fadd_rn(ny, hwy);
-            const double dd = __dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy));
-            PH_MARK(3);
-            if (dd <= Q.eps2) break;
-            if (j > 0 && (double)fabsf(__fadd_rn(dx, pdx)) < 0.01 && (double)fabsf(__fadd_rn(dy, pdy)) < 0.01) {
-                NPx = __fsub_rn(NPx, __fmul_rn(dx, 0.5f));
-                NPy = __fsub_rn(NPy, __fmul_rn(dy, 0.5f));
-                break;
-            }
-            pdx = dx;
-            pdy = dy;
+            PSN_PH_MARK(acc_ph, t_ph, 2);
+            float dx, dy;
+            const double dd = lk_update(A11, A12, A22, D, b1, b2, hwx, hwy, nx, ny, NPx, NPy, dx, dy);
+            PSN_PH_MARK(acc_ph, t_ph, 3);
+            if (lk_stop(dd, Q.eps2, j, dx, dy, pdx, pdy, NPx, NPy)) break;
         }
         LK_STAMP(level * 10 + 7);
         LK_COUNT(level * 10 + 8, jdone);
@@ -1970,14 +1812,14 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
         if (level == 0 && status && A.err && (flags & PSN_LK_GET_MIN_EIGENVALS) == 0) {
             const float qx = __fsub_rn(NPx, hwx), qy = __fsub_rn(NPy, hwy);
             const int iqx = cv_floor(qx), iqy = cv_floor(qy);
-            if (iqx < -w || iqx >= cols || iqy < -h || iqy >= rows) {
+            if (win_outside(iqx, iqy, w, h, cols, rows)) {
                 status = 0;
                 continue;
             }
             int iw00, iw01, iw10, iw11;
             bilin_weights(__fsub_rn(qx, (float)iqx), __fsub_rn(qy, (float)iqy), iw00, iw01, iw10, iw11);
             __syncthreads();  // every wave is done with R (last products) and JP
-            if (!(iqx >= jr_x0 && iqy >= jr_y0 && iqx + w + 1 <= jr_x0 + JRW && iqy + h + 1 <= jr_y0 + JRH)) {
+            if (!(jr_covers(iqx, iqy, w, h, jr_x0, jr_y0, JRW, JRH))) {
                 JPStage<NT> cp;
                 jr_x0 = (iqx - kStJMargin) & ~3;
                 jr_y0 = iqy - kStJMargin;
@@ -2006,15 +1848,13 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                 if (lane == 0) acc = chain_sum16(R, round16i(wh) >> 4);
                 errval = readlane_f(acc, 0);
             }
-            errv = __fdiv_rn(__fmul_rn(errval, 1.f), (float)(32 * wh));
+            errv = lk_err(errval, wh);
         }
     }
     }  // legacy multi-wave iterations
 
     LK_STAMP(61);
-#ifdef PSN_LK_STAMPS
     for (int i = 0; i < 8; i++) LK_COUNT(40 + i, acc_ph[i]);
-#endif
     if (tid == 0) {
         A.next[2 * pi] = NPx;
         A.next[2 * pi + 1] = NPy;
@@ -2023,9 +1863,6 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
     }
     if (A.pyr_ntiles > 0) pyr_tail<NT>(A, smem);
 }
-#undef PH_BEGIN
-#undef PH_MARK
-#undef PH_COUNT
 
 // ---------------------------------------------------------------------------
 // lk_kernel_bx -- box windows (Tracker2D: (int)box.w x (int)box.w backward,
@@ -2046,30 +1883,9 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
 // float in the SSE2 build's order. Otherwise the ordered float chains: terms
 // chain-major into LDS planes, row tile by row tile, one lane per chain.
 // ---------------------------------------------------------------------------
-// Diagnostic phase clocks (PSN_LK_STAMPS, thread 0's view): accumulated
-// s_memtime ticks per phase, written as stamps[wg][0..15] at the end.
-#ifdef PSN_LK_STAMPS
-#define BX_CLK(t) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory")
-#define BX_BEGIN() BX_CLK(bx_t)
-#define BX_MARK(i)                    \
-    do {                              \
-        unsigned long long t_;        \
-        BX_CLK(t_);                   \
-        bx_acc[i] += t_ - bx_t;       \
-        bx_t = t_;                    \
-    } while (0)
-#define BX_COUNT(i) bx_acc[i]++
-#else
-#define BX_BEGIN() \
-    do {           \
-    } while (0)
-#define BX_MARK(i) \
-    do {           \
-    } while (0)
-#define BX_COUNT(i) \
-    do {            \
-    } while (0)
-#endif
+// Diagnostic phase clocks (PSN_LK_STAMPS, psn_lk_stamps.h; thread 0's view):
+// accumulated s_memtime ticks per phase in bx_acc, written as stamps[wg][0..15]
+// at the end.
 template <int UPT, bool NOTAIL>
 __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx(LkLaunchArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -2140,11 +1956,10 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
     }
     int status = 1;
     float errv = 0.f;
-    const float FLT_SCALE = 1.f / (1 << 20);
     int par = 0;
 #ifdef PSN_LK_STAMPS
     unsigned long long bx_acc[16] = {}, bx_t = 0, bx_t0 = 0, bx_r0 = 0;
-    BX_CLK(bx_t0);
+    PSN_CLK_ORDERED(bx_t0);
     bx_t = bx_t0;
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(bx_r0) : : "memory");  // 100 MHz
 #endif
@@ -2177,7 +1992,7 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
         px = __fsub_rn(px, hwx);
         py = __fsub_rn(py, hwy);
         const int ipx = cv_floor(px), ipy = cv_floor(py);
-        if (ipx < -w || ipx >= cols || ipy < -h || ipy >= rows) {
+        if (win_outside(ipx, ipy, w, h, cols, rows)) {
             if (level == 0) {
                 status = 0;
                 errv = 0.f;
@@ -2197,12 +2012,12 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
         // before the A publish barrier, which makes it visible to every wave
         dma_patch<NT>(JR, J, jr_y0, jr_x0, JRW, JRH, JRP4, Q.dv_bxjr);
         barrier_inflight();  // the I patch (waited above) for every wave; J still moving
-        BX_MARK(0);  // level setup + staging
+        PSN_PH_MARK(bx_acc, bx_t, 0);  // level setup + staging
         bx_prio_lo();
 
         // ---- A phase: Scharr + bilinear window values of the thread's units from
         // the I patch bytes; the 15 A chains (sum x class) as runs ----
-        float A11, A12, A22;
+        float sA[3];  // the raw A11, A12, A22 sums
         nwin++;
         {
             const int sh = (ipx - 1) & 3;
@@ -2304,7 +2119,7 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 T[5 + c] = T12[c], M[5 + c] = M12[c], m[5 + c] = m12[c];
                 T[10 + c] = T22[c], M[10 + c] = T22[c], m[10 + c] = 0;
             }
-            BX_MARK(1);  // A window values + runs
+            PSN_PH_MARK(bx_acc, bx_t, 1);  // A window values + runs
             bx_prio_hi();
             int *rec = X + par * 4 * kBxRecInts;
             par ^= 1;
@@ -2315,16 +2130,9 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
             __syncthreads();
             int tot, h0, base0;
             const bool exact = bx_eval<15>(rec, tot, h0, base0);
-            float s3[3];
             if (exact) {
 #pragma unroll
-                for (int s = 0; s < 3; s++) {
-                    float t = rl_f(tot, 5 * s + 4);
-                    if (sse)
-                        t = __fadd_rn(t, __fadd_rn(__fadd_rn(__fadd_rn(rl_f(tot, 5 * s), rl_f(tot, 5 * s + 1)),
-                                                             rl_f(tot, 5 * s + 2)), rl_f(tot, 5 * s + 3)));
-                    s3[s] = t;
-                }
+                for (int s = 0; s < 3; s++) sA[s] = combine_a5([&](int i) { return rl_f(tot, i); }, s, sse);
             } else {
                 // ordered float chains from half wave h0 on (every earlier prefix is an
                 // exact integer: the chains start from base0): tiles of HW half waves
@@ -2501,53 +2309,36 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                     __syncthreads();
                 }
                 if (ftid < 64) {  // wave 0 combines in the SSE2 build's order
-                    const int av = __float_as_int(acc);
 #pragma unroll
                     for (int s = 0; s < 3; s++) {
-                        float t = __int_as_float(__builtin_amdgcn_readlane(av, 5 * s + 4));
-                        if (sse) {
-                            const float c0 = __int_as_float(__builtin_amdgcn_readlane(av, 5 * s));
-                            const float c1 = __int_as_float(__builtin_amdgcn_readlane(av, 5 * s + 1));
-                            const float c2 = __int_as_float(__builtin_amdgcn_readlane(av, 5 * s + 2));
-                            const float c3 = __int_as_float(__builtin_amdgcn_readlane(av, 5 * s + 3));
-                            t = __fadd_rn(t, __fadd_rn(__fadd_rn(__fadd_rn(c0, c1), c2), c3));
-                        }
+                        const float t = combine_a5([&](int i) { return readlane_f(acc, i); }, s, sse);
                         if (ftid == 0) RS[s] = t;
                     }
                 }
                 __syncthreads();
-                s3[0] = RS[0];
-                s3[1] = RS[1];
-                s3[2] = RS[2];
+                sA[0] = RS[0];
+                sA[1] = RS[1];
+                sA[2] = RS[2];
             }
-            BX_MARK(2);  // A publish / eval / serial chains
-            A11 = __fmul_rn(s3[0], FLT_SCALE);
-            A12 = __fmul_rn(s3[1], FLT_SCALE);
-            A22 = __fmul_rn(s3[2], FLT_SCALE);
+            PSN_PH_MARK(bx_acc, bx_t, 2);  // A publish / eval / serial chains
         }
-        float D = __fsub_rn(__fmul_rn(A11, A22), __fmul_rn(A12, A12));
-        {
-            const float dd = __fsub_rn(A11, A22);
-            const float t = __fadd_rn(__fmul_rn(dd, dd), __fmul_rn(__fmul_rn(4.f, A12), A12));
-            const float minEig = __fdiv_rn(__fsub_rn(__fadd_rn(A22, A11), sqrtf(t)), (float)(2 * w * h));
-            if (flags & PSN_LK_GET_MIN_EIGENVALS) errv = minEig;
-            if (minEig < Q.min_eig || D < FLT_EPSILON) {
-                if (level == 0) status = 0;
-                continue;
-            }
+        const LkSolve S = lk_solve(sA[0], sA[1], sA[2], w * h, Q.min_eig);
+        if (flags & PSN_LK_GET_MIN_EIGENVALS) errv = S.minEig;
+        if (!S.ok) {
+            if (level == 0) status = 0;
+            continue;
         }
-        D = __fdiv_rn(1.f, D);
 
         float pdx = 0.f, pdy = 0.f;
         for (int j = 0; j < Q.max_count; j++) {
             const int inx = cv_floor(nx), iny = cv_floor(ny);
-            if (inx < -w || inx >= cols || iny < -h || iny >= rows) {
+            if (win_outside(inx, iny, w, h, cols, rows)) {
                 if (level == 0) status = 0;
                 break;
             }
             int w00, w01, w10, w11;
             bilin_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny), w00, w01, w10, w11);
-            if (!(inx >= jr_x0 && iny >= jr_y0 && inx + w + 1 <= jr_x0 + JRW && iny + h + 1 <= jr_y0 + JRH)) {
+            if (!(jr_covers(inx, iny, w, h, jr_x0, jr_y0, JRW, JRH))) {
                 // every wave's J reads of the previous iteration precede its barrier
                 jr_x0 = (inx - kStJMargin) & ~3;
                 jr_y0 = iny - kStJMargin;
@@ -2555,9 +2346,9 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 dma_wait();
                 __syncthreads();
             }
-            BX_MARK(3);  // iteration head (restage)
+            PSN_PH_MARK(bx_acc, bx_t, 3);  // iteration head (restage)
             bx_prio_lo();
-            BX_COUNT(10);
+            PSN_PH_COUNT(bx_acc, 10);
             nwin++;
             const unsigned W0 = pack_w(w00, w01), W1 = pack_w(w10, w11);
             const int ox = inx - jr_x0, oy = iny - jr_y0, sj = ox & 3;
@@ -2686,26 +2477,21 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 T[c] = T1[c], M[c] = M1[c], m[c] = m1[c];
                 T[5 + c] = T2[c], M[5 + c] = M2[c], m[5 + c] = m2[c];
             }
-            BX_MARK(4);  // b main pass
+            PSN_PH_MARK(bx_acc, bx_t, 4);  // b main pass
             bx_prio_hi();
             int *rec = X + par * 4 * kBxRecInts;
             par ^= 1;
             bx_publish<10>(T, rec, NOTAIL || tB == 0);
-            BX_MARK(9);  // b publish (this wave's scans and records)
+            PSN_PH_MARK(bx_acc, bx_t, 9);  // b publish (this wave's scans and records)
             __syncthreads();
             bx_check<10>(T, M, m, bad, rec, NOTAIL || tB == 0);
             __syncthreads();
             int tot, h0, base0;
             float b1, b2;
             const bool bex = bx_eval<10>(rec, tot, h0, base0);
-            BX_MARK(5);  // b publish + barrier + eval
+            PSN_PH_MARK(bx_acc, bx_t, 5);  // b publish + barrier + eval
             if (bex) {
-                b1 = rl_f(tot, 4);
-                b2 = rl_f(tot, 9);
-                if (sse) {
-                    b1 = __fadd_rn(b1, __fadd_rn(__fadd_rn(rl_f(tot, 0), rl_f(tot, 2)), __fadd_rn(rl_f(tot, 1), rl_f(tot, 3))));
-                    b2 = __fadd_rn(b2, __fadd_rn(__fadd_rn(rl_f(tot, 5), rl_f(tot, 7)), __fadd_rn(rl_f(tot, 6), rl_f(tot, 8))));
-                }
+                combine_b10([&](int i) { return rl_f(tot, i); }, sse, b1, b2);
             } else {
                 // ordered float chains from half wave h0 on, tiles of 32 threads' units,
                 // double-buffered: the threads of tile g+1 write its products while the
@@ -2909,7 +2695,7 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                         if (fl == 0) FLG[b] = tag(g);
                     }
-                    BX_MARK(6);  // serial b: own tiles' products
+                    PSN_PH_MARK(bx_acc, bx_t, 6);  // serial b: own tiles' products
                     if (wv == 0) {
                         for (int g = h0; g <= g_last; g++) {
                             const int b = (g - h0) % 3;
@@ -2935,13 +2721,13 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 write_tile(h0, PL);
                 pad_tile(h0, PL);
                 __syncthreads();
-                BX_MARK(6);  // serial b: first tile's products
+                PSN_PH_MARK(bx_acc, bx_t, 6);  // serial b: first tile's products
                 for (int g = h0, t = 0; g <= g_last; g += HW, t ^= 1) {  // tile = half waves g .. g+HW-1
                     float *cur = PL + t * 2 * PC, *nxt = PL + (t ^ 1) * 2 * PC;
                     if (g + HW <= g_last) write_tile(g + HW, nxt);
 #ifdef PSN_LK_STAMPS
                     unsigned long long tc0, tc1, tc2;
-                    BX_CLK(tc0);
+                    PSN_CLK_ORDERED(tc0);
 #endif
                     if ((ftid >> 6) == 0) {
                         int sa, ta, nsse, ntail;
@@ -2955,35 +2741,22 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                         if (g + HW <= g_last) pad_tile(g + HW, nxt);
                     }
 #ifdef PSN_LK_STAMPS
-                    BX_CLK(tc1);
+                    PSN_CLK_ORDERED(tc1);
 #endif
                     __syncthreads();
 #ifdef PSN_LK_STAMPS
-                    BX_CLK(tc2);
+                    PSN_CLK_ORDERED(tc2);
                     bx_acc[12] += tc1 - tc0;  // (chain lane 0's view) chain sums incl. its own tile writes
                     bx_acc[13] += tc2 - tc1;  // barrier wait
                     bx_acc[14]++;
 #endif
                 }
                 }
-                BX_MARK(7);  // serial b: pipelined products + chains
-                BX_COUNT(11);
+                PSN_PH_MARK(bx_acc, bx_t, 7);  // serial b: pipelined products + chains
+                PSN_PH_COUNT(bx_acc, 11);
                 if (ftid < 64) {  // wave 0 combines in the SSE2 build's order
-                    const int a = __float_as_int(acc);
-                    float r1 = __int_as_float(__builtin_amdgcn_readlane(a, 4));
-                    float r2 = __int_as_float(__builtin_amdgcn_readlane(a, 9));
-                    if (sse) {
-                        const float bb0 = __fadd_rn(__int_as_float(__builtin_amdgcn_readlane(a, 0)),
-                                                    __int_as_float(__builtin_amdgcn_readlane(a, 2)));
-                        const float bb2 = __fadd_rn(__int_as_float(__builtin_amdgcn_readlane(a, 1)),
-                                                    __int_as_float(__builtin_amdgcn_readlane(a, 3)));
-                        const float bb1 = __fadd_rn(__int_as_float(__builtin_amdgcn_readlane(a, 5)),
-                                                    __int_as_float(__builtin_amdgcn_readlane(a, 7)));
-                        const float bb3 = __fadd_rn(__int_as_float(__builtin_amdgcn_readlane(a, 6)),
-                                                    __int_as_float(__builtin_amdgcn_readlane(a, 8)));
-                        r1 = __fadd_rn(r1, __fadd_rn(bb0, bb2));
-                        r2 = __fadd_rn(r2, __fadd_rn(bb1, bb3));
-                    }
+                    float r1, r2;
+                    combine_b10([&](int i) { return readlane_f(acc, i); }, sse, r1, r2);
                     if (ftid == 0) {
                         RS[4] = r1;
                         RS[5] = r2;
@@ -2993,36 +2766,22 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 b1 = RS[4];
                 b2 = RS[5];
             }
-            BX_MARK(8);  // b results
-            b1 = __fmul_rn(b1, FLT_SCALE);
-            b2 = __fmul_rn(b2, FLT_SCALE);
-            const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, b2), __fmul_rn(A22, b1)), D);
-            const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, b1), __fmul_rn(A11, b2)), D);
-            nx = __fadd_rn(nx, dx);
-            ny = __fadd_rn(ny, dy);
-            NPx = __fadd_rn(nx, hwx);
-            NPy = __fadd_rn(ny, hwy);
-            const double dd = __dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy));
-            if (dd <= Q.eps2) break;
-            if (j > 0 && (double)fabsf(__fadd_rn(dx, pdx)) < 0.01 && (double)fabsf(__fadd_rn(dy, pdy)) < 0.01) {
-                NPx = __fsub_rn(NPx, __fmul_rn(dx, 0.5f));
-                NPy = __fsub_rn(NPy, __fmul_rn(dy, 0.5f));
-                break;
-            }
-            pdx = dx;
-            pdy = dy;
+            PSN_PH_MARK(bx_acc, bx_t, 8);  // b results
+            float dx, dy;
+            const double dd = lk_update(S.A11, S.A12, S.A22, S.invD, b1, b2, hwx, hwy, nx, ny, NPx, NPy, dx, dy);
+            if (lk_stop(dd, Q.eps2, j, dx, dy, pdx, pdy, NPx, NPy)) break;
         }
 
         if (level == 0 && status && A.err && (flags & PSN_LK_GET_MIN_EIGENVALS) == 0) {
             const float qx = __fsub_rn(NPx, hwx), qy = __fsub_rn(NPy, hwy);
             const int iqx = cv_floor(qx), iqy = cv_floor(qy);
-            if (iqx < -w || iqx >= cols || iqy < -h || iqy >= rows) {
+            if (win_outside(iqx, iqy, w, h, cols, rows)) {
                 status = 0;
                 continue;
             }
             int w00, w01, w10, w11;
             bilin_weights(__fsub_rn(qx, (float)iqx), __fsub_rn(qy, (float)iqy), w00, w01, w10, w11);
-            if (!(iqx >= jr_x0 && iqy >= jr_y0 && iqx + w + 1 <= jr_x0 + JRW && iqy + h + 1 <= jr_y0 + JRH)) {
+            if (!(jr_covers(iqx, iqy, w, h, jr_x0, jr_y0, JRW, JRH))) {
                 __syncthreads();  // a serial b pass may still read nothing of JR, but be safe
                 jr_x0 = (iqx - kStJMargin) & ~3;
                 jr_y0 = iqy - kStJMargin;
@@ -3088,14 +2847,14 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 __syncthreads();
                 errval = RS[8];
             }
-            errv = __fdiv_rn(__fmul_rn(errval, 1.f), (float)(32 * w * h));
+            errv = lk_err(errval, w * h);
         }
     }
 
 #ifdef PSN_LK_STAMPS
     {
         unsigned long long t_end;
-        BX_CLK(t_end);
+        PSN_CLK_ORDERED(t_end);
         bx_acc[15] = t_end - bx_t0;
         unsigned long long r1;
         unsigned hwid, xcc;
@@ -3124,89 +2883,71 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
     }
 }
 
+// The instantiations of each kernel family, written ONCE: the launch dispatch and
+// the dynamic-LDS attribute loop of lk_kernels_init are both generated from these
+// lists, so a variant cannot launch without its attribute.
+// lk_kernel_bx: X(UPT units per thread, NOTAIL).
+#define PSN_BX_KERNELS(X)                                         \
+    X(4, true) X(4, false) X(8, true) X(8, false) X(10, true)     \
+    X(10, false) X(12, true) X(12, false) X(16, true) X(16, false)
+// lk_kernel_st: X(NT workgroup size, EPT window pixels per thread, E one-wave
+// rows per lane (0: multi-wave iterations), OCC workgroups per CU the build is
+// held to). The OCC 3 builds are the one-wave kernels held to 168 VGPRs: three
+// workgroups per CU when the launch has more points than two per CU can hold.
+#define PSN_ST_KERNELS(X)                                                                 \
+    X(64, 2, 0, 1) X(64, 4, 0, 1) X(128, 2, 0, 1) X(128, 4, 0, 1) X(256, 2, 0, 1)         \
+    X(512, 1, 0, 1) X(512, 2, 0, 1) X(256, 2, 4, 1) X(256, 2, 7, 1) X(256, 2, 8, 1)       \
+    X(256, 4, 8, 1) X(256, 2, 16, 1) X(256, 4, 16, 1) X(256, 4, 0, 1) X(256, 2, 4, 3)     \
+    X(256, 2, 7, 3) X(256, 2, 8, 3)
+
 hipError_t launch_lk_bx(const LkLaunchArgs &a, int total_wgs, int upt, bool notail, int lds_bytes, hipStream_t s) {
     if (total_wgs <= 0) return hipSuccess;
     const dim3 grid(total_wgs), block(kBxNT);
-#define PSN_BX_CASE(U)                                                                              \
-    case U:                                                                                         \
-        if (notail)                                                                                 \
-            hipLaunchKernelGGL((lk_kernel_bx<U, true>), grid, block, lds_bytes, s, a);              \
-        else                                                                                        \
-            hipLaunchKernelGGL((lk_kernel_bx<U, false>), grid, block, lds_bytes, s, a);             \
-        break;
-    switch (upt) {
-        PSN_BX_CASE(4)
-        PSN_BX_CASE(8)
-        PSN_BX_CASE(10)
-        PSN_BX_CASE(12)
-        PSN_BX_CASE(16)
-        default: return hipErrorInvalidValue;
+#define PSN_BX_LAUNCH(U, NOTAIL)                                                         \
+    if (upt == U && notail == NOTAIL) {                                                  \
+        hipLaunchKernelGGL((lk_kernel_bx<U, NOTAIL>), grid, block, lds_bytes, s, a);     \
+        return hipGetLastError();                                                        \
     }
-#undef PSN_BX_CASE
-    return hipGetLastError();
+    PSN_BX_KERNELS(PSN_BX_LAUNCH)
+#undef PSN_BX_LAUNCH
+    return hipErrorInvalidValue;
 }
 
-hipError_t launch_lk(const LkLaunchArgs &a, int total_wgs, int threads, int lds_bytes, bool single_tile, hipStream_t s) {
+hipError_t launch_lk_st(const LkLaunchArgs &a, int total_wgs, int nt, int ept, int e, int occ, int lds_bytes,
+                        hipStream_t s) {
     if (total_wgs <= 0) return hipSuccess;
     const dim3 grid(total_wgs);
-    if (single_tile) {
-        // threads encodes (workgroup size, pixels per thread, one-wave rows): E * 1000 + NT * 10 + EPT
-        switch (threads) {
-            case 642: hipLaunchKernelGGL((lk_kernel_st<64, 2, 0>), grid, dim3(64), lds_bytes, s, a); break;
-            case 644: hipLaunchKernelGGL((lk_kernel_st<64, 4, 0>), grid, dim3(64), lds_bytes, s, a); break;
-            case 1282: hipLaunchKernelGGL((lk_kernel_st<128, 2, 0>), grid, dim3(128), lds_bytes, s, a); break;
-            case 1284: hipLaunchKernelGGL((lk_kernel_st<128, 4, 0>), grid, dim3(128), lds_bytes, s, a); break;
-            case 2562: hipLaunchKernelGGL((lk_kernel_st<256, 2, 0>), grid, dim3(256), lds_bytes, s, a); break;
-            case 5121: hipLaunchKernelGGL((lk_kernel_st<512, 1, 0>), grid, dim3(512), lds_bytes, s, a); break;
-            case 5122: hipLaunchKernelGGL((lk_kernel_st<512, 2, 0>), grid, dim3(512), lds_bytes, s, a); break;
-            case 6562: hipLaunchKernelGGL((lk_kernel_st<256, 2, 4>), grid, dim3(256), lds_bytes, s, a); break;
-            case 9562: hipLaunchKernelGGL((lk_kernel_st<256, 2, 7>), grid, dim3(256), lds_bytes, s, a); break;
-            case 10562: hipLaunchKernelGGL((lk_kernel_st<256, 2, 8>), grid, dim3(256), lds_bytes, s, a); break;
-            case 10564: hipLaunchKernelGGL((lk_kernel_st<256, 4, 8>), grid, dim3(256), lds_bytes, s, a); break;
-            case 18562: hipLaunchKernelGGL((lk_kernel_st<256, 2, 16>), grid, dim3(256), lds_bytes, s, a); break;
-            case 18564: hipLaunchKernelGGL((lk_kernel_st<256, 4, 16>), grid, dim3(256), lds_bytes, s, a); break;
-            case 2564: hipLaunchKernelGGL((lk_kernel_st<256, 4, 0>), grid, dim3(256), lds_bytes, s, a); break;
-            // one-wave kernels held to 168 VGPRs: three workgroups per CU when the
-            // launch has more points than two per CU can hold (+200000)
-            case 206562: hipLaunchKernelGGL((lk_kernel_st<256, 2, 4, 3>), grid, dim3(256), lds_bytes, s, a); break;
-            case 209562: hipLaunchKernelGGL((lk_kernel_st<256, 2, 7, 3>), grid, dim3(256), lds_bytes, s, a); break;
-            case 210562: hipLaunchKernelGGL((lk_kernel_st<256, 2, 8, 3>), grid, dim3(256), lds_bytes, s, a); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (threads) {
-            case 64: hipLaunchKernelGGL(lk_kernel<64>, grid, dim3(64), lds_bytes, s, a); break;
-            case 128: hipLaunchKernelGGL(lk_kernel<128>, grid, dim3(128), lds_bytes, s, a); break;
-            default: hipLaunchKernelGGL(lk_kernel<256>, grid, dim3(256), lds_bytes, s, a); break;
-        }
+#define PSN_ST_LAUNCH(NT, EPT, E, OCC)                                                              \
+    if (nt == NT && ept == EPT && e == E && occ == OCC) {                                           \
+        hipLaunchKernelGGL((lk_kernel_st<NT, EPT, E, OCC>), grid, dim3(NT), lds_bytes, s, a);       \
+        return hipGetLastError();                                                                   \
+    }
+    PSN_ST_KERNELS(PSN_ST_LAUNCH)
+#undef PSN_ST_LAUNCH
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_lk(const LkLaunchArgs &a, int total_wgs, int threads, int lds_bytes, hipStream_t s) {
+    if (total_wgs <= 0) return hipSuccess;
+    const dim3 grid(total_wgs);
+    switch (threads) {
+        case 64: hipLaunchKernelGGL(lk_kernel<64>, grid, dim3(64), lds_bytes, s, a); break;
+        case 128: hipLaunchKernelGGL(lk_kernel<128>, grid, dim3(128), lds_bytes, s, a); break;
+        default: hipLaunchKernelGGL(lk_kernel<256>, grid, dim3(256), lds_bytes, s, a); break;
     }
     return hipGetLastError();
 }
 
 hipError_t lk_kernels_init() {
     const int max_lds = 160 * 1024;
+#define PSN_BX_FN(U, NOTAIL) (const void *)lk_kernel_bx<U, NOTAIL>,
+#define PSN_ST_FN(NT, EPT, E, OCC) (const void *)lk_kernel_st<NT, EPT, E, OCC>,
+    const void *fns[] = {(const void *)lk_kernel<64>, (const void *)lk_kernel<128>, (const void *)lk_kernel<256>,
+                         PSN_ST_KERNELS(PSN_ST_FN) PSN_BX_KERNELS(PSN_BX_FN) (const void *)pyramid_kernel};
+#undef PSN_BX_FN
+#undef PSN_ST_FN
     hipError_t e;
-    if ((e = hipFuncSetAttribute((const void *)lk_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void *)lk_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void *)lk_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    const void *st[] = {(const void *)lk_kernel_st<64, 2, 0>,   (const void *)lk_kernel_st<64, 4, 0>,
-                        (const void *)lk_kernel_st<128, 2, 0>,  (const void *)lk_kernel_st<128, 4, 0>,
-                        (const void *)lk_kernel_st<256, 2, 0>,  (const void *)lk_kernel_st<256, 4, 0>,
-                        (const void *)lk_kernel_st<512, 1, 0>,  (const void *)lk_kernel_st<512, 2, 0>,
-                        (const void *)lk_kernel_st<256, 2, 4>,  (const void *)lk_kernel_st<256, 2, 7>,
-                        (const void *)lk_kernel_st<256, 2, 8>,  (const void *)lk_kernel_st<256, 4, 8>,
-                        (const void *)lk_kernel_st<256, 2, 16>, (const void *)lk_kernel_st<256, 4, 16>,
-                        (const void *)lk_kernel_st<256, 2, 4, 3>,  (const void *)lk_kernel_st<256, 2, 7, 3>,
-                        (const void *)lk_kernel_st<256, 2, 8, 3>};
-    for (const void *f : st)
-        if ((e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void *)pyramid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
-    const void *bx[] = {(const void *)lk_kernel_bx<4, false>, (const void *)lk_kernel_bx<8, false>,
-                        (const void *)lk_kernel_bx<10, false>, (const void *)lk_kernel_bx<12, false>,
-                        (const void *)lk_kernel_bx<4, true>, (const void *)lk_kernel_bx<8, true>,
-                        (const void *)lk_kernel_bx<10, true>, (const void *)lk_kernel_bx<12, true>,
-                        (const void *)lk_kernel_bx<16, false>, (const void *)lk_kernel_bx<16, true>};
-    for (const void *f : bx)
+    for (const void *f : fns)
         if ((e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) != hipSuccess) return e;
     if ((e = lg_kernels_init()) != hipSuccess) return e;
     return gridfast_kernels_init();

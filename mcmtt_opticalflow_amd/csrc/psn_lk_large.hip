@@ -239,26 +239,9 @@ __device__ __forceinline__ float lg_tiles(int qs, int NQ, float *buf, int nch, f
     return acc;
 }
 
-// Diagnostic phase clocks (PSN_LK_STAMPS build, tools/lg_stamps.py): accumulated
-// s_memtime ticks per phase of each point, thread 0's view, stamps[point][0..15].
-#ifdef PSN_LK_STAMPS
-#define LG_CLK(t) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory")
-#define LG_MARK(i)                    \
-    do {                              \
-        unsigned long long t_;        \
-        LG_CLK(t_);                   \
-        lg_acc[i] += t_ - lg_t;       \
-        lg_t = t_;                    \
-    } while (0)
-#define LG_COUNT(i) lg_acc[i]++
-#else
-#define LG_MARK(i) \
-    do {           \
-    } while (0)
-#define LG_COUNT(i) \
-    do {            \
-    } while (0)
-#endif
+// Diagnostic phase clocks (PSN_LK_STAMPS build, psn_lk_stamps.h; tools/lg_stamps.py):
+// accumulated s_memtime ticks per phase of each point in lg_acc, thread 0's view,
+// written as stamps[point][0..23] at the end.
 
 constexpr int kLgMB = 4;  // quads per batch of slot loads in the passes over the window
 
@@ -284,7 +267,6 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
     int2 *XREC = (int2 *)U;  // b fallback run records [chain][thread]
 #endif
     uint8_t *const slot = (uint8_t *)A.lg_ws + (long long)blockIdx.x * A.lg_slot * 8;
-    const float FLT_SCALE = 1.f / (1 << 20);
     int par = 0;
 
     for (int gi = blockIdx.x; gi < A.lk_wgs; gi += gridDim.x) {
@@ -322,7 +304,7 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
         unsigned nwin = 0;  // window passes (A phase + iterations): the sample count / (w*h)
 #ifdef PSN_LK_STAMPS
         unsigned long long lg_acc[24] = {}, lg_t = 0, lg_t0 = 0;
-        LG_CLK(lg_t0);
+        PSN_CLK_ORDERED(lg_t0);
         lg_t = lg_t0;
 #endif
 
@@ -336,8 +318,7 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
             bool jr_valid = false;
             int jr_x0 = 0, jr_y0 = 0;
             auto window_j = [&](int inx, int iny, int w00, int w01, int w10, int w11) {
-                if (jrm && !(jr_valid && inx >= jr_x0 && iny >= jr_y0 && inx + w + 1 <= jr_x0 + JRW &&
-                             iny + h + 1 <= jr_y0 + JRH)) {
+                if (jrm && !(jr_valid && jr_covers(inx, iny, w, h, jr_x0, jr_y0, JRW, JRH))) {
                     // every reader of the previous copy passed a barrier since
                     jr_x0 = (inx - kStJMargin) & ~3;
                     jr_y0 = iny - kStJMargin;
@@ -367,6 +348,8 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
             px = __fsub_rn(px, hwx);
             py = __fsub_rn(py, hwy);
             const int ipx = cv_floor(px), ipy = cv_floor(py);
+            // (win_outside, written out at this kernel's three sites: through the helper the
+            // compiler folds the tests differently and the kernel's VGPR count changes)
             if (ipx < -w || ipx >= cols || ipy < -h || ipy >= rows) {
                 if (level == 0) {
                     status = 0;
@@ -397,7 +380,7 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                         dma_rows<NT>(Pimg, I, ipy + r0 - 1, ipx - 1, w + 3, th + 3, PM);
                         dma_wait();
                         __syncthreads();
-                        LG_MARK(7);  // band staging
+                        PSN_PH_MARK(lg_acc, lg_t, 7);  // band staging
                         Walk wk;
                         wk.init(tid, NT, QW);
                         for (int qb = tid; qb < th * QW; qb += NT, wk.step()) {
@@ -409,7 +392,7 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                             XPs[idx] = make_uint2(xp[0], xp[1]);
                             YPs[idx] = make_uint2(yp[0], yp[1]);
                         }
-                        LG_MARK(9);  // band quads
+                        PSN_PH_MARK(lg_acc, lg_t, 9);  // band quads
                     }
                 };
                 if (interior)
@@ -418,11 +401,11 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                     band(std::false_type());
             }
             __syncthreads();  // the window values of every band for every thread
-            LG_MARK(0);  // A phase: window values
+            PSN_PH_MARK(lg_acc, lg_t, 0);  // A phase: window values
 
             // ---- A phase (2): the 15 A chains (sum x class) as runs over the
             // thread's quads, the block check, ordered chains if inexact ----
-            float A11, A12, A22;
+            float s3[3];   // the raw A11, A12, A22 sums
             int gmax = 0;  // max |Ix|, |Iy| of the thread's pixels (exactness of the b terms)
             {
                 int T11[5] = {0, 0, 0, 0, 0}, T22[5] = {0, 0, 0, 0, 0}, T12[5] = {0, 0, 0, 0, 0};
@@ -485,16 +468,9 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                 __syncthreads();
                 int tot, h0, base0;
                 const bool exact = bx_eval_t<15>(rec, tot, h0, base0);
-                float s3[3];
                 if (exact) {
 #pragma unroll
-                    for (int s = 0; s < 3; s++) {
-                        float t = rl_f(tot, 5 * s + 4);
-                        if (sse)
-                            t = __fadd_rn(t, __fadd_rn(__fadd_rn(__fadd_rn(rl_f(tot, 5 * s), rl_f(tot, 5 * s + 1)),
-                                                                 rl_f(tot, 5 * s + 2)), rl_f(tot, 5 * s + 3)));
-                        s3[s] = t;
-                    }
+                    for (int s = 0; s < 3; s++) s3[s] = combine_a5([&](int i) { return rl_f(tot, i); }, s, sse);
                 } else {
                     // ordered chains from thread h0's run on (every earlier prefix is an
                     // exact integer: the chain lanes start from base0)
@@ -538,17 +514,9 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                     };
                     float acc = lg_tiles<3, TQ>(qs, NQ, PL, 15, (float)base0, loadA, storeA, geoA, [&](int) {});
                     if (tid < 64) {  // wave 0 combines in the SSE2 build's order
-                        const int av = __float_as_int(acc);
 #pragma unroll
                         for (int s = 0; s < 3; s++) {
-                            float t = __int_as_float(__builtin_amdgcn_readlane(av, 5 * s + 4));
-                            if (sse) {
-                                const float c0 = __int_as_float(__builtin_amdgcn_readlane(av, 5 * s));
-                                const float c1 = __int_as_float(__builtin_amdgcn_readlane(av, 5 * s + 1));
-                                const float c2 = __int_as_float(__builtin_amdgcn_readlane(av, 5 * s + 2));
-                                const float c3 = __int_as_float(__builtin_amdgcn_readlane(av, 5 * s + 3));
-                                t = __fadd_rn(t, __fadd_rn(__fadd_rn(__fadd_rn(c0, c1), c2), c3));
-                            }
+                            const float t = combine_a5([&](int i) { return readlane_f(acc, i); }, s, sse);
                             if (tid == 0) RS[s] = t;
                         }
                     }
@@ -557,23 +525,14 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                     s3[1] = RS[1];
                     s3[2] = RS[2];
                 }
-                A11 = __fmul_rn(s3[0], FLT_SCALE);
-                A12 = __fmul_rn(s3[1], FLT_SCALE);
-                A22 = __fmul_rn(s3[2], FLT_SCALE);
             }
-            LG_MARK(1);  // A chains
-            float D = __fsub_rn(__fmul_rn(A11, A22), __fmul_rn(A12, A12));
-            {
-                const float dd = __fsub_rn(A11, A22);
-                const float t = __fadd_rn(__fmul_rn(dd, dd), __fmul_rn(__fmul_rn(4.f, A12), A12));
-                const float minEig = __fdiv_rn(__fsub_rn(__fadd_rn(A22, A11), sqrtf(t)), (float)(2 * w * h));
-                if (flags & PSN_LK_GET_MIN_EIGENVALS) errv = minEig;
-                if (minEig < Q.min_eig || D < FLT_EPSILON) {
-                    if (level == 0) status = 0;
-                    continue;
-                }
+            PSN_PH_MARK(lg_acc, lg_t, 1);  // A chains
+            const LkSolve S = lk_solve(s3[0], s3[1], s3[2], w * h, Q.min_eig);
+            if (flags & PSN_LK_GET_MIN_EIGENVALS) errv = S.minEig;
+            if (!S.ok) {
+                if (level == 0) status = 0;
+                continue;
             }
-            D = __fdiv_rn(1.f, D);
 
             float pdx = 0.f, pdy = 0.f;
             for (int j = 0; j < Q.max_count; j++) {
@@ -637,8 +596,8 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                         quad(IPs[ix], XPs[ix], YPs[ix]);
                     }
                 }
-                LG_MARK(2);  // main pass
-                LG_COUNT(10);
+                PSN_PH_MARK(lg_acc, lg_t, 2);  // main pass
+                PSN_PH_COUNT(lg_acc, 10);
                 // every term is an exact float unless |d| * |g| > 2^24; a run past
                 // [-2^25, 2^25] (terms < 2^26: seen before any wrap) cannot be exact
                 bool bad = (long long)dmax * gmax > (long long)kExact;
@@ -658,17 +617,12 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                 __syncthreads();
                 int tot, h0, base0;
                 const bool bex = bx_eval_t<10>(rec, tot, h0, base0);
-                LG_MARK(3);  // publish / check / eval
+                PSN_PH_MARK(lg_acc, lg_t, 3);  // publish / check / eval
                 float b1, b2;
                 if (bex) {
-                    b1 = rl_f(tot, 4);
-                    b2 = rl_f(tot, 9);
-                    if (sse) {
-                        b1 = __fadd_rn(b1, __fadd_rn(__fadd_rn(rl_f(tot, 0), rl_f(tot, 2)), __fadd_rn(rl_f(tot, 1), rl_f(tot, 3))));
-                        b2 = __fadd_rn(b2, __fadd_rn(__fadd_rn(rl_f(tot, 5), rl_f(tot, 7)), __fadd_rn(rl_f(tot, 6), rl_f(tot, 8))));
-                    }
+                    combine_b10([&](int i) { return rl_f(tot, i); }, sse, b1, b2);
                 } else {
-                    LG_COUNT(11);
+                    PSN_PH_COUNT(lg_acc, 11);
                     // ordered float chains from thread h0's run on (chain lanes: wave 0,
                     // lanes 0-9, from their exact prefixes base0), tiles of TQ quads
                     const int qs = min(h0 * K, NQ);
@@ -710,17 +664,17 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                             }
                         }
                     };
-                    LG_MARK(4);
+                    PSN_PH_MARK(lg_acc, lg_t, 4);
                     auto markB = [&](int i) {
                         if (i == 0) {
-                            LG_MARK(18);  // ordered b chains: pads of the next tile
-                            LG_COUNT(14);
+                            PSN_PH_MARK(lg_acc, lg_t, 18);  // ordered b chains: pads of the next tile
+                            PSN_PH_COUNT(lg_acc, 14);
                         } else if (i == 1) {
-                            LG_MARK(13);  // barrier wait
+                            PSN_PH_MARK(lg_acc, lg_t, 13);  // barrier wait
                         } else if (i == 2) {
-                            LG_MARK(16);  // writes, loads, tile geometry
+                            PSN_PH_MARK(lg_acc, lg_t, 16);  // writes, loads, tile geometry
                         } else {
-                            LG_MARK(17);  // chain sums
+                            PSN_PH_MARK(lg_acc, lg_t, 17);  // chain sums
                         }
                     };
                     // ---- parity records (psn_lk_xb.h): every thread's run of every chain
@@ -777,7 +731,7 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                         const int pbase = (wv > 0 ? EP[12] : 0) + (wv > 1 ? EP[13] : 0) + (wv > 2 ? EP[14] : 0);
                         const int ptotal = EP[12] + EP[13] + EP[14] + EP[15];
                         if (ptotal > kLgPoolBytes / 4) return false;
-                        LG_MARK(19);  // xb: prefixes, guard, keys, pool scan
+                        PSN_PH_MARK(lg_acc, lg_t, 19);  // xb: prefixes, guard, keys, pool scan
                         // replay: each thread's run of every chain; first terms kept, the rest
                         // from two representatives of either parity near B + first term (key
                         // 23: one exact replay); HARD runs' terms into the pool
@@ -857,7 +811,7 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                                 quad(IPs[ix], XPs[ix], YPs[ix]);
                             }
                         }
-                        LG_MARK(20);  // xb: replay
+                        PSN_PH_MARK(lg_acc, lg_t, 20);  // xb: replay
                         // records (the b tiles region; its last readers passed a barrier)
                         bool fail = false;
                         if (tid >= fs) {
@@ -882,13 +836,13 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                         if (fail) EP[3] = 1;  // (no __syncthreads_or: it takes static LDS)
                         __syncthreads();
                         if (EP[3]) return false;
-                        LG_MARK(21);  // xb: records
+                        PSN_PH_MARK(lg_acc, lg_t, 21);  // xb: records
                         // the walk: chain lane c from the exact prefix before half wave h0
                         if (tid < 10) {
                             const int last = min(kXbRecThreads, (NQ + K - 1) / K);
                             acc_out = xb_walk(XREC + tid * kXbRecThreads, POOL, fs, last, (float)base0);
                         }
-                        LG_MARK(22);  // xb: walk
+                        PSN_PH_MARK(lg_acc, lg_t, 22);  // xb: walk
                         return true;
                     };
                     float acc;
@@ -899,23 +853,10 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
 #else
                     const float acc = lg_tiles<2, TQ>(qs, NQ, PL, 10, (float)base0, loadB, storeB, geoB, markB);
 #endif
-                    LG_MARK(5);  // ordered b chains
+                    PSN_PH_MARK(lg_acc, lg_t, 5);  // ordered b chains
                     if (tid < 64) {  // wave 0 combines in the SSE2 build's order
-                        const int a = __float_as_int(acc);
-                        float r1 = __int_as_float(__builtin_amdgcn_readlane(a, 4));
-                        float r2 = __int_as_float(__builtin_amdgcn_readlane(a, 9));
-                        if (sse) {
-                            const float bb0 = __fadd_rn(__int_as_float(__builtin_amdgcn_readlane(a, 0)),
-                                                        __int_as_float(__builtin_amdgcn_readlane(a, 2)));
-                            const float bb2 = __fadd_rn(__int_as_float(__builtin_amdgcn_readlane(a, 1)),
-                                                        __int_as_float(__builtin_amdgcn_readlane(a, 3)));
-                            const float bb1 = __fadd_rn(__int_as_float(__builtin_amdgcn_readlane(a, 5)),
-                                                        __int_as_float(__builtin_amdgcn_readlane(a, 7)));
-                            const float bb3 = __fadd_rn(__int_as_float(__builtin_amdgcn_readlane(a, 6)),
-                                                        __int_as_float(__builtin_amdgcn_readlane(a, 8)));
-                            r1 = __fadd_rn(r1, __fadd_rn(bb0, bb2));
-                            r2 = __fadd_rn(r2, __fadd_rn(bb1, bb3));
-                        }
+                        float r1, r2;
+                        combine_b10([&](int i) { return readlane_f(acc, i); }, sse, r1, r2);
                         if (tid == 0) {
                             RS[4] = r1;
                             RS[5] = r2;
@@ -925,24 +866,10 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                     b1 = RS[4];
                     b2 = RS[5];
                 }
-                LG_MARK(6);  // results
-                b1 = __fmul_rn(b1, FLT_SCALE);
-                b2 = __fmul_rn(b2, FLT_SCALE);
-                const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, b2), __fmul_rn(A22, b1)), D);
-                const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, b1), __fmul_rn(A11, b2)), D);
-                nx = __fadd_rn(nx, dx);
-                ny = __fadd_rn(ny, dy);
-                NPx = __fadd_rn(nx, hwx);
-                NPy = __fadd_rn(ny, hwy);
-                const double dd = __dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy));
-                if (dd <= Q.eps2) break;
-                if (j > 0 && (double)fabsf(__fadd_rn(dx, pdx)) < 0.01 && (double)fabsf(__fadd_rn(dy, pdy)) < 0.01) {
-                    NPx = __fsub_rn(NPx, __fmul_rn(dx, 0.5f));
-                    NPy = __fsub_rn(NPy, __fmul_rn(dy, 0.5f));
-                    break;
-                }
-                pdx = dx;
-                pdy = dy;
+                PSN_PH_MARK(lg_acc, lg_t, 6);  // results
+                float dx, dy;
+                const double dd = lk_update(S.A11, S.A12, S.A22, S.invD, b1, b2, hwx, hwy, nx, ny, NPx, NPy, dx, dy);
+                if (lk_stop(dd, Q.eps2, j, dx, dy, pdx, pdy, NPx, NPy)) break;
             }
 
             if (level == 0 && status && A.err && (flags & PSN_LK_GET_MIN_EIGENVALS) == 0) {
@@ -1010,14 +937,14 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                     __syncthreads();
                     errval = RS[8];
                 }
-                errv = __fdiv_rn(__fmul_rn(errval, 1.f), (float)(32 * w * h));
+                errv = lk_err(errval, w * h);
             }
         }
 
 #ifdef PSN_LK_STAMPS
         {
             unsigned long long t_end;
-            LG_CLK(t_end);
+            PSN_CLK_ORDERED(t_end);
             lg_acc[15] = t_end - lg_t0;
             if (tid == 0 && A.stamps)
                 for (int i = 0; i < 24; i++) A.stamps[(size_t)g * 64 + i] = lg_acc[i];
