@@ -306,6 +306,60 @@ int psn_gridfast_detect_device_sets(psn_lk_ctx *ctx, int nset, const int *slots,
                                     const psn_gridfast_params *p, uint32_t seed, float *d_out_xy, int *d_out_count,
                                     int *d_out_total);
 
+/* ---- RGB box histograms: Associator3D's appearance feature on the device ----
+ * Replaces, per reported box, the crop of the raw colour frame and
+ *   GetRGBFeature(patch, 16)      psn_where/PSNWhere_Associator3D.cpp:2542-2556
+ *     -> psn::histogram(channel, 16)   psn_where/PSNWhere_Utils.cpp:445-460
+ * called at :1160-1166 (RGBFeatureHead) and :1208-1214 (RGBFeatureTail): the
+ * frame is in device memory when the boxes become known, and in a one-process-
+ * per-GPU run only there. Per rect, 3 x 16 counters in the order R[16], G[16],
+ * B[16] (vconcat, :2551-2552) over exactly its w * h pixels, bin =
+ * floor(value / 16.0) = value >> 4; the frame is BGR (R = byte 2 of a pixel).
+ * The integer counts and the pixel count are the contract. The reference's
+ * double feature is derived from them on the host (include/psn_tracker2d.h):
+ *   feature[i] = (double)count[i] * (1.0 / (double)n_pixels)
+ * [OCV246]: `featureR / numPixels` on a CV_64F Mat is a scaled conversion by
+ * alpha = 1.0 / numPixels in OpenCV 2.4.6, a product, not count / n. OpenCV is
+ * not available to this project's tests, so this is a reading of
+ * its source that no test here pins against the library.
+ * A rect with w <= 0 or h <= 0 is an empty crop: all counts 0. (The reference
+ * would fail an OpenCV assertion; this ABI returns codes and never aborts.) */
+#define PSN_RGBHIST_BINS 16
+typedef struct psn_rgbhist_rect {
+    const uint8_t *frame; /* device pointer to pixel (0, 0) of a BGR frame, 3 bytes per pixel */
+    int stride;           /* bytes per row (any value >= 3 * width; rows need no alignment) */
+    int x, y, w, h;       /* pixels, inside the frame: 0 <= x, x + w <= width, the same for y */
+} psn_rgbhist_rect;
+/* Raw and asynchronous: counts nrect rects (a device array of descriptors, on
+ * any number of frames) into d_counts[nrect][48] in ONE launch on `hip_stream`
+ * (hipStream_t as void*, NULL = the default stream) of the current device.
+ * d_counts is zeroed here, on the stream. The caller owns the frames and keeps
+ * them, the descriptors and d_counts valid until the work is done; the rects
+ * are not checked (they are device data) and must lie inside their frames. */
+int psn_rgbhist_device(const psn_rgbhist_rect *d_rects, int nrect, uint32_t *d_counts, void *hip_stream);
+/* On the colour frames of a context's ring slots, after the pattern of
+ * psn_gridfast_detect_device_sets: set i = nrects[i] rects {x, y, w, h} on the
+ * colour frame last pushed into ring slot slots[i], the sets' rects consecutive
+ * in `rects` and their counters in `counts` (host, [sum nrects][48]). The rects
+ * are clipped to the frame here (x < 0 -> 0, y < 0 -> 0, x + w > width ->
+ * w = width - x, y + h > height -> h = height - y); an empty rect gives zeros.
+ * One launch for all sets; synchronous, on a stream of the context's own that
+ * waits for each slot's upload / decode / build but not for queued LK work.
+ * The colour source of a slot is what its last push read:
+ *   psn_lk_push_frame_async / _jpeg  the slot's staging buffer: stays valid
+ *                                    until the next push into that slot, which
+ *                                    waits for the histogram's read;
+ *   psn_lk_push_frame_device         the caller's frame: it must stay valid and
+ *                                    unchanged until this call returns;
+ *   psn_lk_push_frame                the context's one upload buffer: valid only
+ *                                    until the next psn_lk_push_frame (or
+ *                                    psn_calc_optical_flow_pyr_lk) into any
+ *                                    slot; after that PSN_LK_ERR_SLOT.
+ * PSN_LK_ERR_SLOT also for a slot out of range or never filled;
+ * PSN_LK_ERR_UNSUPPORTED when the slot's last frame had 1 channel. */
+int psn_lk_box_histograms(psn_lk_ctx *ctx, int nset, const int *slots, const int *nrects, const int *rects,
+                          uint32_t *counts);
+
 /* ---- multi-GPU: per-camera tracklet slots all-gathered over RCCL/xGMI ----
  * Replaces the in-process std::vector<stTrack2DResult> hand-off into
  * CPSNWhere_Associator3D::Run (psn_where/PSNWhere.cpp:253, 264, 269). */

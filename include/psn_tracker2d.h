@@ -309,6 +309,76 @@ size_t psn_t2d_result_slot_bytes(int max_objects, int max_rects);
 int psn_t2d_pack_result(const psn_track2d_result *r, void *slot, size_t slot_bytes);
 int psn_t2d_unpack_result(const void *slot, size_t slot_bytes, psn_track2d_result *r);
 
+/* ---- appearance: the RGB histogram Associator3D takes of every reported box ----
+ * Tracklet2D_UpdateTracklets crops each box of the result out of the raw
+ * colour frame and keeps GetRGBFeature(patch, 16) as RGBFeatureHead /
+ * RGBFeatureTail (psn_where/PSNWhere_Associator3D.cpp:1160-1166, :1208-1214;
+ * GetRGBFeature :2542-2556; psn::histogram, PSNWhere_Utils.cpp:445-460), which
+ * ComputeRGBCost compares (:2020-2024). The frames of a camera live on the
+ * device of the rank that tracks it, so the histograms are taken there
+ * (psn_lk_box_histograms, include/psn_lk.h) and travel with the results.
+ *
+ * psn_t2d_appearance_rect: the crop of `box` in a width x height frame,
+ *   c = box.cropWithSize(width, height)          PSNWhere_Types.h:146-153, :1130
+ *   r = cv::Rect((int)c.x, (int)c.y, (int)c.w, (int)c.h)   truncation, :181
+ *   x < 0 -> 0; y < 0 -> 0; x + w > width -> w = width - x;
+ *   y + h > height -> h = height - y             :1161-1164, in that order
+ * rect_out = {x, y, w, h}. A crop with w <= 0 or h <= 0 is empty: rect_out =
+ * {0, 0, 0, 0}, and its record has n_pixels = 0, all counts and features 0 (the
+ * reference would fail an OpenCV assertion on it; this ABI returns codes and
+ * never aborts). A coordinate beyond the int range saturates before the cast.
+ * Host arithmetic only. PSN_LK_ERR_ARG: NULL rect_out, width or height <= 0, a
+ * NaN coordinate. */
+#define PSN_T2D_APPEARANCE_BINS 48 /* R[16], G[16], B[16] (vconcat, :2551-2552) */
+int psn_t2d_appearance_rect(psn_rect box, int width, int height, int rect_out[4]);
+
+/* One object's appearance. counts and n_pixels (= rect w * h) are exact and are
+ * the contract; feature[i] = (double)counts[i] * (1.0 / (double)n_pixels), 0.0
+ * when n_pixels = 0 -- [OCV246]: OpenCV 2.4.6 evaluates `featureR / numPixels`
+ * on a CV_64F Mat as a conversion scaled by alpha = 1.0 / numPixels (a product,
+ * not count / n); read from its source, not pinned against the library here. */
+typedef struct psn_t2d_appearance {
+    unsigned id;                                    /* psn_object2d::id */
+    int rect[4];                                    /* psn_t2d_appearance_rect of the object's box */
+    unsigned n_pixels;
+    uint32_t counts[PSN_T2D_APPEARANCE_BINS];
+    double feature[PSN_T2D_APPEARANCE_BINS];
+} psn_t2d_appearance;
+/* feature[] of a record from its counts and n_pixels (the formula above). */
+void psn_t2d_appearance_normalize(psn_t2d_appearance *a);
+
+/* The appearance of every results[c].objects[k] of every camera c of the group,
+ * taken on frame `frame_idx` of that camera: out[c][k] (capacity cap_out[c]
+ * records) gets the object's id, crop, counts and feature. One kernel launch
+ * covers all cameras, one host sync. Valid after psn_t2d_group_complete of
+ * that frame, and after psn_t2d_group_complete_next(frame_idx -> the next):
+ * the frame is found in the camera's ring by its index, not as "the newest".
+ * results = the records complete wrote (or any boxes to be cropped from that
+ * frame). PSN_LK_ERR_SLOT when the frame has left the 4-frame ring,
+ * PSN_T2D_ERR_CAPACITY when a cap_out[c] is below results[c].num_objects,
+ * PSN_LK_ERR_UNSUPPORTED for a camera whose frame was pushed with 1 channel.
+ * A frame pushed with psn_t2d_group_push_frame_device must still be valid and
+ * unchanged (psn_lk_box_histograms). Changes nothing of the group's tracking
+ * state. */
+int psn_t2d_group_appearance(psn_t2d_group *g, unsigned frame_idx, const psn_track2d_result *results,
+                             psn_t2d_appearance *const *out, const int *cap_out);
+
+/* Fixed-size binary slot of one camera's appearances, all-gathered next to its
+ * result slot (psn_t2d_pack_result, whose format is unchanged): little-endian,
+ * self-describing:
+ *   u32 magic 'PT2A', u32 version 1, u32 cam_id, u32 frame_idx, u32 nobj,
+ *   u32 bytes_used,
+ *   nobj x {u32 id, u32 n_pixels, i32 rect[4], u32 counts[48]}
+ * The doubles do not travel: unpack recomputes them (psn_t2d_appearance_normalize).
+ * pack: PSN_T2D_ERR_CAPACITY when the slot is too small. unpack: PSN_LK_ERR_ARG
+ * for a bad magic, version or length, PSN_T2D_ERR_CAPACITY when cap < nobj;
+ * cam_id / frame_idx may be NULL. */
+size_t psn_t2d_appearance_slot_bytes(int max_objects);
+int psn_t2d_pack_appearance(unsigned cam_id, unsigned frame_idx, const psn_t2d_appearance *a, int n, void *slot,
+                            size_t slot_bytes);
+int psn_t2d_unpack_appearance(const void *slot, size_t slot_bytes, unsigned *cam_id, unsigned *frame_idx,
+                              psn_t2d_appearance *out, int cap, int *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,20 @@ class GridFastParams(ctypes.Structure):
     ]
 
 
+RGBHIST_BINS = 16  # PSN_RGBHIST_BINS: per rect 3 x 16 counters, R G B
+
+
+class RgbHistRect(ctypes.Structure):  # psn_rgbhist_rect
+    _fields_ = [
+        ("frame", ctypes.c_void_p),
+        ("stride", ctypes.c_int),
+        ("x", ctypes.c_int),
+        ("y", ctypes.c_int),
+        ("w", ctypes.c_int),
+        ("h", ctypes.c_int),
+    ]
+
+
 def header_functions() -> list[str]:
     """Names of every function declared in include/psn_lk.h and psn_sgsmooth.h."""
     src = "".join(open(p).read() for p in HEADER_PATHS)
@@ -207,6 +221,9 @@ def load(path: str | None = None):
     if hasattr(L, "psn_gridfast_detect_device_sets"):  # (absent from the A/B experiments' older builds only)
         L.psn_gridfast_detect_device_sets.argtypes = [vp, ip, vp, vp, vp, ctypes.POINTER(GridFastParams),
                                                       ctypes.c_uint32, vp, vp, vp]
+    if hasattr(L, "psn_rgbhist_device"):  # (absent from the A/B experiments' older builds only)
+        L.psn_rgbhist_device.argtypes = [vp, ip, vp, vp]
+        L.psn_lk_box_histograms.argtypes = [vp, ip, vp, vp, vp, vp]
     L.psn_sg_create.argtypes = [ip, ip, ip, ip, ip, ctypes.POINTER(vp)]
     L.psn_sg_destroy.argtypes = [vp]
     L.psn_sg_destroy.restype = None

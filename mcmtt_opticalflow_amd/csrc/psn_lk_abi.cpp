@@ -24,6 +24,7 @@
 #include "psn_lk.h"
 #include "psn_jpeg.h"
 #include "psn_gridfast.h"
+#include "psn_rgbhist.h"
 #include "psn_lk_kernels.h"
 
 using psn::LevelDev;
@@ -86,6 +87,26 @@ struct psn_lk_ctx {
     std::vector<uint8_t *> d_stage;
     std::vector<size_t> stage_cap;
     std::vector<int> used_slots;  // scratch of track_device_impl
+    // psn_lk_box_histograms: per slot the colour source its last push read (the
+    // slot's staging buffer, the caller's device frame, or the shared d_src of a
+    // host push: valid while no later host push has overwritten it, src_gen)
+    struct ColorSrc {
+        const uint8_t *p = nullptr;
+        int stride = 0, channels = 0;
+        bool shared = false;  // p = d_src
+        unsigned gen = 0;     // src_gen of that push
+    };
+    std::vector<ColorSrc> color_src;
+    unsigned src_gen = 0;  // host pushes through d_src so far
+    // its own stream (created at the first call): the histograms of frame t do
+    // not queue behind frame t+1's LK launches
+    hipStream_t hist_stream = nullptr;
+    hipEvent_t hist_ev = nullptr;             // orders hist_stream after the context stream where no slot event does
+    psn_rgbhist_rect *h_hist_rects = nullptr;  // pinned
+    psn_rgbhist_rect *d_hist_rects = nullptr;
+    uint32_t *h_hist_counts = nullptr;  // pinned
+    uint32_t *d_hist_counts = nullptr;
+    size_t hist_cap = 0;  // rects
     psn_jpeg_ctx *jpeg = nullptr;  // psn_lk_push_frame_jpeg's decoder (on the ingest stream)
     uint8_t *d_pyr = nullptr;
     LevelDev *d_slots = nullptr;
@@ -411,6 +432,7 @@ int psn_lk_create(int device, int width, int height, int ring_slots, int max_lev
     c->ready_rec.assign(c->nslots, 0);
     c->build_gen.assign(c->nslots, 0);
     c->waited.assign(c->nslots, {});
+    c->color_src.assign(c->nslots, {});
     c->d_stage.assign(c->nslots, nullptr);
     c->stage_cap.assign(c->nslots, 0);
     c->copy_done.assign(c->nslots, nullptr);
@@ -432,6 +454,7 @@ void psn_lk_destroy(psn_lk_ctx *c) {
         if (is) (void)hipStreamSynchronize(is);
     for (hipStream_t cs : c->copy_streams)
         if (cs) (void)hipStreamSynchronize(cs);
+    if (c->hist_stream) (void)hipStreamSynchronize(c->hist_stream);
     for (auto *v : {&c->ev_push, &c->ev_track, &c->slot_ready, &c->copy_done})
         for (auto e : *v)
             if (e) (void)hipEventDestroy(e);
@@ -462,6 +485,12 @@ void psn_lk_destroy(psn_lk_ctx *c) {
                     (void *)c->d_err, (void *)c->d_status, (void *)c->d_gf_kp, (void *)c->d_gf_cnt, (void *)c->d_gf_xy,
                     (void *)c->d_gf_oc, (void *)c->d_gf_ot})
         if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->d_hist_rects, (void *)c->d_hist_counts})
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->h_hist_rects, (void *)c->h_hist_counts})
+        if (p) (void)hipHostFree(p);
+    if (c->hist_ev) (void)hipEventDestroy(c->hist_ev);
+    if (c->hist_stream) (void)hipStreamDestroy(c->hist_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     for (hipStream_t is : c->ingest_streams)
         if (is) (void)hipStreamDestroy(is);
@@ -621,7 +650,10 @@ static void ev_unref(psn_lk_ctx *c, psn_lk_ctx::SharedEv *e) {
 // it becomes that stream's free event of every slot read (a later build into
 // one of them waits for it). An event returns to the pool when no slot refers
 // to it; re-recording a pooled event never moves a live reference.
-static int record_slots_free(psn_lk_ctx *c, const int *slots, int n) {
+static int record_slots_free_on(psn_lk_ctx *c, const int *slots, int n, hipStream_t s);
+static int record_slots_free(psn_lk_ctx *c, const int *slots, int n) { return record_slots_free_on(c, slots, n, c->stream); }
+// The same for a launch on stream s.
+static int record_slots_free_on(psn_lk_ctx *c, const int *slots, int n, hipStream_t s) {
     psn_lk_ctx::SharedEv *e = nullptr;
     if (!c->ev_free.empty()) {
         e = c->ev_free.back();
@@ -635,13 +667,13 @@ static int record_slots_free(psn_lk_ctx *c, const int *slots, int n) {
         }
         c->ev_all.push_back(e);
     }
-    HIPCHK(c, hipEventRecord(e->e, c->stream));
+    HIPCHK(c, hipEventRecord(e->e, s));
     for (int i = 0; i < n; i++) {
         const int slot = slots[i];
         if (slot < 0 || slot >= c->nslots) continue;
         bool found = false;
         for (auto &se : c->slot_free[slot])
-            if (se.first == c->stream) {
+            if (se.first == s) {
                 if (se.second != e) {
                     e->refs++;
                     ev_unref(c, se.second);
@@ -652,7 +684,7 @@ static int record_slots_free(psn_lk_ctx *c, const int *slots, int n) {
             }
         if (!found) {
             e->refs++;
-            c->slot_free[slot].emplace_back(c->stream, e);
+            c->slot_free[slot].emplace_back(s, e);
         }
     }
     if (e->refs == 0) c->ev_free.push_back(e);
@@ -745,6 +777,7 @@ int psn_lk_push_frame_jpeg(psn_lk_ctx *c, int slot, const uint8_t *jpeg, size_t 
     rc = psn_jpeg_decode_device(c->jpeg, jpeg, len, c->d_stage[slot], (int)row);
     if (rc) return set_err(c, rc, "JPEG decode: %s", psn_jpeg_last_error(c->jpeg));
     c->filled[slot] = 1;
+    c->color_src[slot] = {c->d_stage[slot], (int)row, 3, false, 0};
     return launch_build(c, build_args(c, slot, c->d_stage[slot], (int)row, 3), c->ingest_stream, slot);
 }
 
@@ -761,6 +794,10 @@ int psn_lk_push_frame_async(psn_lk_ctx *c, int slot, const uint8_t *host, int st
     // the staging buffer is read only by this slot's previous build (its ready
     // event); the build waits for the upload and for every read of the slot
     if (c->ready_rec[slot]) HIPCHK(c, hipStreamWaitEvent(cs, c->slot_ready[slot], 0));
+    // ... and by a box-histogram launch (psn_lk_box_histograms, on its own stream)
+    if (c->hist_stream)
+        for (auto &se : c->slot_free[slot])
+            if (se.first == c->hist_stream) HIPCHK(c, hipStreamWaitEvent(cs, se.second->e, 0));
     if ((size_t)stride == row)  // contiguous rows: one linear copy (the DMA engine's fast path)
         HIPCHK(c, hipMemcpyAsync(c->d_stage[slot], host, need, hipMemcpyHostToDevice, cs));
     else
@@ -770,6 +807,7 @@ int psn_lk_push_frame_async(psn_lk_ctx *c, int slot, const uint8_t *host, int st
     if (rc) return rc;
     HIPCHK(c, hipStreamWaitEvent(s, c->copy_done[slot], 0));
     c->filled[slot] = 1;
+    c->color_src[slot] = {c->d_stage[slot], (int)row, channels, false, 0};
     return launch_build(c, build_args(c, slot, c->d_stage[slot], (int)row, channels), s, slot);
 }
 
@@ -777,7 +815,9 @@ int psn_lk_push_frame_device(psn_lk_ctx *c, int slot, const uint8_t *dev, int st
     if (!c || !dev || (channels != 1 && channels != 3) || stride < c->width * channels) return PSN_LK_ERR_ARG;
     if (slot < 0 || slot >= c->user_slots) return set_err(c, PSN_LK_ERR_SLOT, "slot %d out of range", slot);
     HIPCHK(c, hipSetDevice(c->device));
-    return push_device_impl(c, slot, dev, stride, channels);
+    const int rc = push_device_impl(c, slot, dev, stride, channels);
+    if (!rc) c->color_src[slot] = {dev, stride, channels, false, 0};
+    return rc;
 }
 
 static int push_host_impl(psn_lk_ctx *c, int slot, const uint8_t *host, int stride, int channels) {
@@ -799,7 +839,9 @@ static int push_host_impl(psn_lk_ctx *c, int slot, const uint8_t *host, int stri
     int rc = ce == hipSuccess ? push_device_impl(c, slot, c->d_src, (int)row, channels)
                               : set_err(c, PSN_LK_ERR_HIP, "hipMemcpy2DAsync: %s", hipGetErrorString(ce));
     c->overlap = mode;
+    c->src_gen++;  // d_src holds this frame now: the colour source of earlier host pushes is gone
     if (rc) return rc;
+    c->color_src[slot] = {c->d_src, (int)row, channels, true, c->src_gen};
     HIPCHK(c, hipStreamSynchronize(s));  // the host frame belongs to the caller after return
     return PSN_LK_OK;
 }
@@ -1661,6 +1703,101 @@ int psn_gridfast_detect(psn_lk_ctx *c, int slot, const int *rois, int nroi, cons
         HIPCHK(c, hipMemcpyAsync(out_xy, c->d_gf_xy, (size_t)nroi * p.cap * 2 * sizeof(float), hipMemcpyDeviceToHost,
                                  c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PSN_LK_OK;
+}
+
+// ---- RGB box histograms (include/psn_lk.h; kernel in psn_rgbhist.hip) ----
+
+int psn_rgbhist_device(const psn_rgbhist_rect *d_rects, int nrect, uint32_t *d_counts, void *hip_stream) {
+    if (nrect < 0 || (nrect > 0 && (!d_rects || !d_counts))) return PSN_LK_ERR_ARG;
+    return psn::launch_rgbhist(d_rects, nrect, d_counts, 0, (hipStream_t)hip_stream) == hipSuccess ? PSN_LK_OK
+                                                                                                  : PSN_LK_ERR_HIP;
+}
+
+int psn_lk_box_histograms(psn_lk_ctx *c, int nset, const int *slots, const int *nrects, const int *rects,
+                          uint32_t *counts) {
+    if (!c || nset < 0 || (nset > 0 && (!slots || !nrects))) return PSN_LK_ERR_ARG;
+    long long total = 0;
+    for (int i = 0; i < nset; i++) {
+        if (nrects[i] < 0) return set_err(c, PSN_LK_ERR_ARG, "box histograms: set %d has %d rects", i, nrects[i]);
+        total += nrects[i];
+    }
+    if (total > INT32_MAX / psn::kRhBins || (total > 0 && (!rects || !counts))) return PSN_LK_ERR_ARG;
+    std::vector<int> used;  // distinct slots with rects
+    for (int i = 0; i < nset; i++) {
+        const int slot = slots[i];
+        if (slot < 0 || slot >= c->user_slots || !c->filled[slot] || !c->color_src[slot].p)
+            return set_err(c, PSN_LK_ERR_SLOT, "box histograms: slot %d not filled", slot);
+        const psn_lk_ctx::ColorSrc &cs = c->color_src[slot];
+        if (cs.channels != 3)
+            return set_err(c, PSN_LK_ERR_UNSUPPORTED, "box histograms: slot %d holds a %d-channel frame", slot, cs.channels);
+        if (cs.shared && (cs.gen != c->src_gen || cs.p != c->d_src))
+            return set_err(c, PSN_LK_ERR_SLOT, "box histograms: a later host push replaced slot %d's colour frame", slot);
+        if (nrects[i] > 0 && std::find(used.begin(), used.end(), slot) == used.end()) used.push_back(slot);
+    }
+    if (total == 0) return PSN_LK_OK;
+    const int n = (int)total;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->hist_stream) {
+        HIPCHK(c, hipStreamCreateWithFlags(&c->hist_stream, hipStreamNonBlocking));
+        HIPCHK(c, hipEventCreateWithFlags(&c->hist_ev, kSlotEventFlags));
+    }
+    if (c->hist_cap < (size_t)n) {
+        HIPCHK(c, hipStreamSynchronize(c->hist_stream));
+        for (void **p : {(void **)&c->d_hist_rects, (void **)&c->d_hist_counts})
+            if (*p) (void)hipFree(*p), *p = nullptr;
+        for (void **p : {(void **)&c->h_hist_rects, (void **)&c->h_hist_counts})
+            if (*p) (void)hipHostFree(*p), *p = nullptr;
+        c->hist_cap = 0;
+        const size_t cap = std::max<size_t>(64, (size_t)n + (size_t)n / 2);
+        HIPCHK(c, hipMalloc(&c->d_hist_rects, cap * sizeof(psn_rgbhist_rect)));
+        HIPCHK(c, hipMalloc(&c->d_hist_counts, cap * psn::kRhBins * sizeof(uint32_t)));
+        HIPCHK(c, hipHostMalloc(&c->h_hist_rects, cap * sizeof(psn_rgbhist_rect), 0));
+        HIPCHK(c, hipHostMalloc(&c->h_hist_counts, cap * psn::kRhBins * sizeof(uint32_t), 0));
+        c->hist_cap = cap;
+    }
+    // The frames must be complete: a deferred build of a slot runs first (its
+    // source is ordered by the context stream), and the slot's ready event,
+    // recorded behind the build that read the source, covers the upload or decode
+    // and, for a device frame, the context-stream work that produced it.
+    for (int slot : used) {
+        if (c->pend && c->pend_slot == slot) {
+            int rc = flush_pending(c);
+            if (rc) return rc;
+        }
+        if (c->ready_rec[slot]) {
+            HIPCHK(c, hipStreamWaitEvent(c->hist_stream, c->slot_ready[slot], 0));
+        } else {  // no build event: order by the context stream
+            HIPCHK(c, hipEventRecord(c->hist_ev, c->stream));
+            HIPCHK(c, hipStreamWaitEvent(c->hist_stream, c->hist_ev, 0));
+        }
+    }
+    int bands = 1;
+    for (int i = 0, k = 0; i < nset; i++) {
+        const psn_lk_ctx::ColorSrc &cs = c->color_src[slots[i]];
+        for (int j = 0; j < nrects[i]; j++, k++) {
+            const int *r = rects + 4 * (size_t)k;
+            // the four clamps of PSNWhere_Associator3D.cpp:1161-1164, in that order
+            long long x = r[0], y = r[1], w = r[2], h = r[3];
+            if (x < 0) x = 0;
+            if (y < 0) y = 0;
+            if (x + w > c->width) w = c->width - x;
+            if (y + h > c->height) h = c->height - y;
+            if (w <= 0 || h <= 0) x = y = w = h = 0;  // an empty crop
+            c->h_hist_rects[k] = psn_rgbhist_rect{cs.p, cs.stride, (int)x, (int)y, (int)w, (int)h};
+            bands = std::max(bands, psn::rgbhist_bands((int)w, (int)h));
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_hist_rects, c->h_hist_rects, (size_t)n * sizeof(psn_rgbhist_rect), hipMemcpyHostToDevice,
+                             c->hist_stream));
+    HIPCHK(c, psn::launch_rgbhist(c->d_hist_rects, n, c->d_hist_counts, bands, c->hist_stream));
+    // a later push into these slots overwrites their staging buffers only after this read
+    int rc = record_slots_free_on(c, used.data(), (int)used.size(), c->hist_stream);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_hist_counts, c->d_hist_counts, (size_t)n * psn::kRhBins * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost, c->hist_stream));
+    HIPCHK(c, hipStreamSynchronize(c->hist_stream));
+    memcpy(counts, c->h_hist_counts, (size_t)n * psn::kRhBins * sizeof(uint32_t));
     return PSN_LK_OK;
 }
 

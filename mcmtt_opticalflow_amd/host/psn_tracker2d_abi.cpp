@@ -621,4 +621,48 @@ int psn_t2d_group_trackers(psn_t2d_group *g, int cam, psn_t2d_tracker *out, int 
     return 0;
 }
 
+// The appearance of every reported object of every camera on frame frame_idx:
+// the crops on the host, all cameras' histograms in one launch
+// (psn_lk_box_histograms: set c = camera c's rects on the ring slot of its frame).
+int psn_t2d_group_appearance(psn_t2d_group *g, unsigned frame_idx, const psn_track2d_result *results,
+                             psn_t2d_appearance *const *out, const int *cap_out) {
+    if (!g || !results || !out || !cap_out) return PSN_LK_ERR_ARG;
+    const size_t C = g->io().size();
+    std::vector<int> slots(C), nrects(C), rects;
+    size_t total = 0;
+    for (size_t c = 0; c < C; c++) {
+        const psn_track2d_result &r = results[c];
+        if (r.num_objects < 0 || (r.num_objects > 0 && (!r.objects || !out[c]))) return PSN_LK_ERR_ARG;
+        if (r.num_objects > cap_out[c]) return PSN_T2D_ERR_CAPACITY;
+        const int rc = g->flow.SlotOfFrame(c, frame_idx, &slots[c]);
+        if (rc) return gset(g, rc);
+        nrects[c] = r.num_objects;
+        total += (size_t)r.num_objects;
+    }
+    rects.resize(4 * total);
+    for (size_t c = 0, k = 0; c < C; c++)
+        for (int i = 0; i < results[c].num_objects; i++, k++) {
+            const int rc = psn_t2d_appearance_rect(results[c].objects[i].box, g->flow.Width(), g->flow.Height(),
+                                                   &rects[4 * k]);
+            if (rc) return rc;
+        }
+    std::vector<uint32_t> counts((size_t)PSN_T2D_APPEARANCE_BINS * total);
+    const int rc = psn_lk_box_histograms(g->flow.LkContext(), (int)C, slots.data(), nrects.data(), rects.data(),
+                                         counts.data());
+    if (rc) {
+        g->err = std::string("psn_lk_box_histograms: ") + psn_lk_last_error(g->flow.LkContext());
+        return rc;
+    }
+    for (size_t c = 0, k = 0; c < C; c++)
+        for (int i = 0; i < results[c].num_objects; i++, k++) {
+            psn_t2d_appearance &a = out[c][i];
+            a.id = results[c].objects[i].id;
+            for (int j = 0; j < 4; j++) a.rect[j] = rects[4 * k + (size_t)j];
+            a.n_pixels = (unsigned)a.rect[2] * (unsigned)a.rect[3];
+            std::memcpy(a.counts, &counts[(size_t)PSN_T2D_APPEARANCE_BINS * k], sizeof a.counts);
+            psn_t2d_appearance_normalize(&a);
+        }
+    return 0;
+}
+
 }  // extern "C"

@@ -147,6 +147,7 @@ int Tracker2DFlow::InitializeCameras(const std::vector<unsigned> &camIDs, int wi
         cams_[c].nstaged = 0;
     }
     filled_.assign((size_t)nslots, 0);
+    slot_frame_.assign((size_t)nslots, -1);
     // stream priorities: the backward chains (three dependent launches per frame)
     // are the frame's critical path; the forward calls fill the compute units they
     // leave free instead of taking half of them (the device dispatches waiting
@@ -1473,7 +1474,8 @@ int Tracker2DFlow::TrackFrame(const std::vector<Detection> &dets, const std::vec
 // Adopt every camera's staged frame as frame t (the ring advances: the oldest
 // slot becomes the next staging slot; Run's buffer circulation, :310-316) and
 // set up the pass over io (forward calls not yet attached).
-int Tracker2DFlow::AdoptFrames(std::vector<CamFrame> &io, bool gridfast, std::vector<PassCam> &pass) {
+int Tracker2DFlow::AdoptFrames(std::vector<CamFrame> &io, bool gridfast, std::vector<PassCam> &pass,
+                               unsigned frameIdx) {
     if (io.size() != cams_.size()) return PSN_LK_ERR_ARG;
     for (size_t c = 0; c < cams_.size(); c++) {
         if (cams_[c].nstaged == 0) {
@@ -1493,6 +1495,7 @@ int Tracker2DFlow::AdoptFrames(std::vector<CamFrame> &io, bool gridfast, std::ve
         std::rotate(cam.spares, cam.spares + 1, cam.spares + kT2dStaging);
         cam.spares[kT2dStaging - 1] = oldest;
         cam.nstaged--;
+        slot_frame_[(size_t)cam.ring[kT2dInterval - 1]] = (long long)frameIdx;
         PassCam &p = pass[c];
         p.cam = c;
         p.dets = &io[c].dets;
@@ -1502,6 +1505,19 @@ int Tracker2DFlow::AdoptFrames(std::vector<CamFrame> &io, bool gridfast, std::ve
         io[c].objects.clear();
     }
     return PSN_LK_OK;
+}
+
+int Tracker2DFlow::SlotOfFrame(size_t cam, unsigned frameIdx, int *slot) {
+    if (cam >= cams_.size() || !slot) return PSN_LK_ERR_ARG;
+    for (int i = kT2dInterval - 1; i >= 0; i--) {
+        const int s = cams_[cam].ring[i];
+        if (filled_[(size_t)s] && slot_frame_[(size_t)s] == (long long)frameIdx) {
+            *slot = s;
+            return PSN_LK_OK;
+        }
+    }
+    err_ = "camera " + std::to_string(cam) + ": frame " + std::to_string(frameIdx) + " is not in the ring";
+    return PSN_LK_ERR_SLOT;
 }
 
 void Tracker2DFlow::UnadoptFrames() {
@@ -1531,7 +1547,7 @@ int Tracker2DFlow::RunLaunch(unsigned frameIdx, std::vector<CamFrame> &io, bool 
         pre_io_ = nullptr;
         return PSN_LK_OK;
     }
-    int rc = AdoptFrames(io, gridfast, run_pass_);
+    int rc = AdoptFrames(io, gridfast, run_pass_, frameIdx);
     if (rc) return rc;
     run_frame_ = frameIdx;
     run_gridfast_ = gridfast;
@@ -1599,7 +1615,7 @@ int Tracker2DFlow::RunComplete(std::vector<CamFrame> &io, std::vector<CamFrame> 
     // frame t+1: its forward calls straight from frame t's chains (every detection
     // of frame t becomes a tracker), then its features and chains
     auto prelaunch = [&]() {
-        prc = AdoptFrames(*next, nextGridfast, pre);
+        prc = AdoptFrames(*next, nextGridfast, pre, nextFrameIdx);
         if (prc) {
             pre.clear();
             return;

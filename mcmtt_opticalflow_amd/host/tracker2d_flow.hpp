@@ -127,6 +127,11 @@ class Tracker2DFlow {
     // RunLaunch of that frame (e.g. with corrected detections) may follow.
     bool FrameCompleted() const { return frame_completed_; }
     const std::deque<Tracker2D *> &ActiveTrackers(size_t cam) const { return cams_[cam].active; }
+    // The LK ring slot that holds frame frameIdx of camera `cam` (the frames a
+    // Run adopted, newest first), or PSN_LK_ERR_SLOT once it has left the ring.
+    int SlotOfFrame(size_t cam, unsigned frameIdx, int *slot);
+    int Width() const { return width_; }
+    int Height() const { return height_; }
     // diagnostic: accumulated host microseconds from RunComplete's entry to its
     // phases (copies + next chains enqueued, device done, unpacked, matched, next
     // forward enqueued) and the number of RunComplete calls; reset on read
@@ -271,7 +276,8 @@ class Tracker2DFlow {
     int stage_ = 0;  // staging set of the next chain launch
     void *ev_chain_ = nullptr, *ev_fwd_ = nullptr;  // hipEvent_t: a pass's result copies done
     bool wait_chain_ = false, wait_fwd_ = false;
-    int AdoptFrames(std::vector<CamFrame> &io, bool gridfast, std::vector<PassCam> &pass);
+    int AdoptFrames(std::vector<CamFrame> &io, bool gridfast, std::vector<PassCam> &pass, unsigned frameIdx);
+    std::vector<long long> slot_frame_;  // per LK slot: the frame index it was adopted as, or -1
     void UnadoptFrames();  // AdoptFrames undone: frame t's slot back to staging, the oldest back in the ring
     bool frame_completed_ = false;
     std::vector<PassCam> run_pass_;  // the pass between RunLaunch and RunComplete

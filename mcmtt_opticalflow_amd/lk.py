@@ -220,6 +220,24 @@ class LKContext:
             k += m
         return out
 
+    def box_histograms(self, slot_rect_sets):
+        """psn_lk_box_histograms: slot_rect_sets = [(slot, rects), ...], rects =
+        (n, 4) ints x, y, w, h on the colour frame last pushed into `slot`
+        (clipped to the frame; an empty rect counts nothing). One launch for all
+        sets. Returns, per set, an (n, 48) uint32 array: R[16], G[16], B[16]."""
+        sets = [np.asarray(r, dtype=np.int32).reshape(-1, 4) for _, r in slot_rect_sets]
+        sl = np.ascontiguousarray(np.array([s for s, _ in slot_rect_sets], np.int32))
+        nr = np.ascontiguousarray(np.array([r.shape[0] for r in sets], np.int32))
+        r = np.ascontiguousarray(np.concatenate(sets + [np.zeros((0, 4), np.int32)]))
+        counts = np.zeros((max(r.shape[0], 1), 3 * _lib.RGBHIST_BINS), np.uint32)
+        self._check(self._L.psn_lk_box_histograms(self._h, len(sets), sl.ctypes.data, nr.ctypes.data, r.ctypes.data,
+                                                  counts.ctypes.data), "box_histograms")
+        out, k = [], 0
+        for m in nr:
+            out.append(counts[k:k + m].copy())
+            k += m
+        return out
+
     def track_device_counted(self, queries: list[LkQuery], d_counts: int, d_prev: int, d_next: int, d_status: int,
                              d_err: int | None):
         """Queries sized num_pts (capacity); query i processes d_counts[i] points (device int32)."""
@@ -263,6 +281,14 @@ class LKContext:
             nxt.ctypes.data, st.ctypes.data, er.ctypes.data if er is not None else None, n, ctypes.byref(p)),
             "calc_optical_flow_pyr_lk")
         return nxt, st, er
+
+
+def rgbhist_device(d_rects: int, nrect: int, d_counts: int, stream_ptr: int | None = None):
+    """psn_rgbhist_device: nrect device descriptors (_lib.RgbHistRect) -> d_counts[nrect][48],
+    one asynchronous launch on `stream_ptr` (None: the default stream)."""
+    rc = _lib.load().psn_rgbhist_device(d_rects, nrect, d_counts, stream_ptr)
+    if rc != 0:
+        raise PsnLkError(rc, "psn_rgbhist_device")
 
 
 def calc_optical_flow_pyr_lk(prev_img, next_img, prev_pts, win_size=(21, 21), max_level=3,

@@ -99,6 +99,28 @@ class Track2DResult(ctypes.Structure):  # psn_track2d_result (stTrack2DResult)
                 ("tracker_rects", ctypes.POINTER(Rect))]
 
 
+APPEARANCE_BINS = 48  # PSN_T2D_APPEARANCE_BINS: R[16], G[16], B[16]
+
+
+class Appearance(ctypes.Structure):  # psn_t2d_appearance
+    _fields_ = [("id", ctypes.c_uint), ("rect", ctypes.c_int * 4), ("n_pixels", ctypes.c_uint),
+                ("counts", ctypes.c_uint32 * APPEARANCE_BINS), ("feature", ctypes.c_double * APPEARANCE_BINS)]
+
+    def to_dict(self) -> dict:
+        return {"id": self.id, "rect": tuple(self.rect), "n_pixels": self.n_pixels,
+                "counts": np.array(self.counts, np.uint32), "feature": np.array(self.feature, np.float64)}
+
+    @classmethod
+    def from_dict(cls, d):
+        a = cls()
+        a.id, a.n_pixels = int(d["id"]), int(d["n_pixels"])
+        a.rect[:] = [int(v) for v in d["rect"]]
+        a.counts[:] = [int(v) for v in d["counts"]]
+        if "feature" in d:
+            a.feature[:] = [float(v) for v in d["feature"]]
+        return a
+
+
 def header_functions() -> list[str]:
     src = open(HEADER_PATH).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
@@ -175,12 +197,57 @@ def load():
     L.psn_t2d_group_trackers.argtypes = [vp, ip, ctypes.POINTER(Tracker), ip, ctypes.POINTER(ip)]
     L.psn_t2d_group_debug_host_times.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     L.psn_t2d_group_debug_host_match_times.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+    if hasattr(L, "psn_t2d_appearance_rect"):  # (absent from the A/B experiments' older builds only)
+        L.psn_t2d_appearance_rect.argtypes = [Rect, ip, ip, ctypes.POINTER(ctypes.c_int * 4)]
+        L.psn_t2d_appearance_normalize.argtypes = [ctypes.POINTER(Appearance)]
+        L.psn_t2d_appearance_normalize.restype = None
+        L.psn_t2d_group_appearance.argtypes = [vp, ctypes.c_uint, ctypes.POINTER(Track2DResult), vp, vp]
+        L.psn_t2d_appearance_slot_bytes.argtypes = [ip]
+        L.psn_t2d_appearance_slot_bytes.restype = ctypes.c_size_t
+        L.psn_t2d_pack_appearance.argtypes = [ctypes.c_uint, ctypes.c_uint, vp, ip, vp, ctypes.c_size_t]
+        L.psn_t2d_unpack_appearance.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint),
+                                                ctypes.POINTER(ctypes.c_uint), vp, ip, ctypes.POINTER(ip)]
     _lib = L
     return L
 
 
 def rect(x, y, w, h) -> Rect:
     return Rect(float(x), float(y), float(w), float(h))
+
+
+def appearance_rect(box, width: int, height: int):
+    """psn_t2d_appearance_rect: the crop (x, y, w, h) Associator3D takes of `box` in a
+    width x height frame (PSNWhere_Associator3D.cpp:1130, :1160-1164); (0, 0, 0, 0) = empty."""
+    out = (ctypes.c_int * 4)()
+    rc = load().psn_t2d_appearance_rect(rect(*box), width, height, ctypes.byref(out))
+    if rc:
+        raise T2dError(rc, "psn_t2d_appearance_rect")
+    return tuple(out)
+
+
+def appearance_slot_bytes(max_objects: int) -> int:
+    return load().psn_t2d_appearance_slot_bytes(max_objects)
+
+
+def pack_appearance(cam_id: int, frame_idx: int, apps: list, slot: np.ndarray):
+    """One camera's appearance dicts (Group.appearance) into its 'PT2A' slot (a uint8 array)."""
+    arr = (Appearance * max(len(apps), 1))(*[Appearance.from_dict(a) for a in apps])
+    rc = load().psn_t2d_pack_appearance(cam_id, frame_idx, ctypes.addressof(arr), len(apps), slot.ctypes.data,
+                                        slot.nbytes)
+    if rc:
+        raise T2dError(rc, "psn_t2d_pack_appearance")
+
+
+def unpack_appearance(slot: np.ndarray, cap: int = 64):
+    """-> (cam_id, frame_idx, list of appearance dicts); the doubles are recomputed from the counts."""
+    s = np.ascontiguousarray(slot, np.uint8)
+    arr = (Appearance * max(cap, 1))()
+    cam, frame, n = ctypes.c_uint(), ctypes.c_uint(), ctypes.c_int()
+    rc = load().psn_t2d_unpack_appearance(s.ctypes.data, s.nbytes, ctypes.byref(cam), ctypes.byref(frame),
+                                          ctypes.addressof(arr), cap, ctypes.byref(n))
+    if rc:
+        raise T2dError(rc, "psn_t2d_unpack_appearance")
+    return cam.value, frame.value, [arr[i].to_dict() for i in range(n.value)]
 
 
 def local_search_klt(pre_box, pre: np.ndarray, cur: np.ndarray):
@@ -507,6 +574,17 @@ class Group:
     def run(self, frame_idx: int, dets_per_cam, gridfast: bool = False, seed: int = 0):
         self.launch(frame_idx, dets_per_cam, gridfast, seed)
         return self.complete()
+
+    def appearance(self, frame_idx: int, cap: int | None = None):
+        """psn_t2d_group_appearance on the results of the last complete(): per camera a
+        list of dicts (id, rect, n_pixels, counts[48], feature[48]) of its objects' boxes on
+        frame `frame_idx` (that frame, or the one before the frame launched ahead)."""
+        caps = [self._res[c].num_objects if cap is None else cap for c in range(self.ncams)]
+        arrs = [(Appearance * max(k, 1))() for k in caps]
+        ptrs = (ctypes.c_void_p * self.ncams)(*[ctypes.addressof(a) for a in arrs])
+        cap_arr = (ctypes.c_int * self.ncams)(*caps)
+        self._check(self._L.psn_t2d_group_appearance(self._h, frame_idx, self._res, ptrs, cap_arr), "appearance")
+        return [[arrs[c][i].to_dict() for i in range(self._res[c].num_objects)] for c in range(self.ncams)]
 
     def debug_host_times(self):
         """Mean host microseconds from the entry of complete to its phases since the last call
