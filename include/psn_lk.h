@@ -234,6 +234,9 @@ int psn_lk_timing_launches(psn_lk_ctx *ctx, int cap, double *ms, int *tag, int *
  *   PSN_LK_VARIANT_POISON_LDS  1 = LK launches (single-tile, box, large) fill their LDS
  *                              with pseudo-random words first (tests: a read of unwritten
  *                              LDS shows up)
+ *   PSN_LK_VARIANT_BX_WAVES    0 = planner; 4 = never the two-wave build of lk_kernel_bx;
+ *                              2 = the two-wave build (128 threads, 8 units per thread)
+ *                              for every no-tail box window it fits
  * Queries are split into one launch per window class (single-tile / box kernel
  * per units-per-thread and tail build / row-tiled / large), each sized for its
  * own windows. */
@@ -248,6 +251,7 @@ int psn_lk_timing_launches(psn_lk_ctx *ctx, int cap, double *ms, int *tag, int *
 #define PSN_LK_VARIANT_LG_JR 9
 #define PSN_LK_VARIANT_ST_OVL 10
 #define PSN_LK_VARIANT_POISON_LDS 11
+#define PSN_LK_VARIANT_BX_WAVES 12
 int psn_lk_debug_set_variant(psn_lk_ctx *ctx, int key, int value);
 
 /* Window-sample counter (SURVEY 8(d)'s compute figure): while on, every box-

@@ -129,6 +129,9 @@ struct psn_lk_ctx {
     bool st_ovl = PSN_ST_OVL_DEFAULT != 0;  // ST_OVL 0: every level's A phase in the single-tile prologue
     bool poison_lds = false;                 // POISON_LDS 1: LK launches fill their LDS with a pattern first
     bool box = true;      // BOX 0: box windows run the row-tiled kernel instead of lk_kernel_bx
+    // BX_WAVES: 0 = planner, 4 = never the two-wave box build, 2 = the two-wave
+    // build wherever it fits (psn::bx_two_wave_fits)
+    int bx_waves = 0;
     // TILED_LDS: LDS budget of a tiled-kernel workgroup (bytes); 76 KB keeps two
     // workgroups per CU (Tracker2D box windows: 64x64 backward, 64x160 forward at 1080p)
     int tiled_lds = 76 * 1024;
@@ -856,6 +859,9 @@ int psn_lk_push_frame(psn_lk_ctx *c, int slot, const uint8_t *host, int stride, 
 // Kernel classes of the planner: each track call's queries go to one launch per
 // class (and per box-kernel build), each launch sized for its own windows.
 enum LkClass { kClsSt = 0, kClsBx = 1, kClsTiled = 2, kClsLg = 3 };
+// The planner's default for the windows the two-wave box build fits
+// (PSN_LK_VARIANT_BX_WAVES 0); DESIGN.md section 8 has the measurement behind it.
+constexpr bool kBxPlanTwoWave = true;
 
 // One query as planned: its device descriptor and the kernels that can take it.
 struct PlannedQuery {
@@ -866,6 +872,7 @@ struct PlannedQuery {
     int ow_rows = 1 << 30, ow_lds = 0;  // its one-wave mode
     int ovl_lds = 0;                    // the one-wave mode with the overlapped A phase (0: does not fit)
     int bx_upt = 0, bx_lds = 0;  // box kernel units per thread (0: does not fit)
+    bool bx_w2 = false;          // + the two-wave build (bx_upt = kBxUPT2)
     int tiled_tr = 0;           // row-tiled kernel: tile rows (0: window not LDS-resident)
     int lg_tr = 0;              // large-window kernel: band rows
     bool lg_jr = false;         // + J region in LDS
@@ -987,6 +994,16 @@ static int plan_query(psn_lk_ctx *c, const psn_lk_query &q, bool allow_scratch, 
             pq.bx_upt = upt;
             pq.bx_lds = psn::BxLayout(w, h, upt).total;
             d.bx_tre = psn::bx_err_rows(w, h, psn::BxLayout(w, h, 4).pb);
+            // the two-wave build: the planner's choice for the windows it fits
+            // (kBxPlanTwoWave), or what the BX_WAVES variant says
+            const bool want2 = c->bx_waves == 2 || (c->bx_waves == 0 && kBxPlanTwoWave);
+            if (want2 && psn::bx_two_wave_fits(w, h, notail)) {
+                const psn::BxLayout l2(w, h, psn::kBxUPT2, 1, psn::kBxTile2);
+                pq.bx_w2 = true;
+                pq.bx_upt = psn::kBxUPT2;
+                pq.bx_lds = l2.total;
+                d.bx_tre = psn::bx_err_rows(w, h, l2.pb);
+            }
             d.dv_bxpm = psn::div_magic(psn::bx_pm(w));
             d.dv_bxjr = psn::div_magic(psn::bx_jrp(w) / 4);
         }
@@ -1001,7 +1018,8 @@ static int plan_query(psn_lk_ctx *c, const psn_lk_query &q, bool allow_scratch, 
         pq.cls = kClsSt;
     } else if (pq.bx_upt > 0 && c->box && !c->force_generic && !forced && !(no_bx16 && pq.bx_upt == 16)) {
         pq.cls = kClsBx;
-        pq.key = 10 * pq.bx_upt + ((sse && w % 8 == 0) ? 1 : 0);
+        // (key % 10: 0 = the scalar-tail build, 1 = no-tail, 2 = no-tail two-wave)
+        pq.key = 10 * pq.bx_upt + (pq.bx_w2 ? 2 : (sse && w % 8 == 0) ? 1 : 0);
     } else if (pq.tiled_tr > 0 && (c->force_generic || !c->box || forced)) {
         pq.cls = kClsTiled;
     } else {
@@ -1153,18 +1171,22 @@ static int launch_group(psn_lk_ctx *c, std::vector<PlannedQuery *> &grp, int cls
     if (cls == kClsBx) {
         const int upt = key / 10;
         const bool notail = key % 10 != 0;
+        const int nt = key % 10 == 2 ? psn::kBxNT2 : psn::kBxNT;
+        const int tile = nt == psn::kBxNT2 ? psn::kBxTile2 : psn::kBxTile;
         // the launch's UPT sizes every query's fallback planes; tiles as large as the
-        // kernel's occupancy (bx_occupancy) allows
+        // kernel's occupancy (bx_occupancy) allows -- the two-wave build keeps its
+        // single quarter-wave tiles: a second one would pass the six-per-CU target
         int lds_bx = 0;
         for (int i = 0; i < a.nq; i++) {
             psn::LkQueryDev &d = a.q[i];
             d.bx_hw = 1;
-            while (d.bx_hw < 8 && psn::BxLayout(d.win_w, d.win_h, upt, d.bx_hw + 1).total <= psn::bx_lds_target(upt, notail))
+            while (nt == psn::kBxNT && d.bx_hw < 8 &&
+                   psn::BxLayout(d.win_w, d.win_h, upt, d.bx_hw + 1, tile).total <= psn::bx_lds_target(upt, notail, nt))
                 d.bx_hw++;
-            lds_bx = std::max(lds_bx, psn::BxLayout(d.win_w, d.win_h, upt, d.bx_hw).total);
+            lds_bx = std::max(lds_bx, psn::BxLayout(d.win_w, d.win_h, upt, d.bx_hw, tile).total);
         }
         a.poison_lds = c->poison_lds ? lds_bx : 0;
-        HIPCHK(c, psn::launch_lk_bx(a, wgs, upt, notail, lds_bx, c->stream));
+        HIPCHK(c, psn::launch_lk_bx(a, wgs, upt, notail, nt, lds_bx, c->stream));
         return PSN_LK_OK;
     }
     if (cls == kClsTiled) {
@@ -1261,7 +1283,7 @@ static int track_device_impl(psn_lk_ctx *c, const psn_lk_query *q, int nq, const
                    a.dv_g == b.dv_g && a.dv_cw == b.dv_cw && a.ow_g == b.ow_g && a.ow_rg == b.ow_rg &&
                    a.bx_tre == b.bx_tre && a.bx_hw == b.bx_hw && a.dv_bxpm == b.dv_bxpm && a.dv_bxjr == b.dv_bxjr &&
                    x.single == y.single && x.st_lds == y.st_lds && x.ow_rows == y.ow_rows && x.ow_lds == y.ow_lds &&
-                   x.ovl_lds == y.ovl_lds && x.bx_upt == y.bx_upt && x.bx_lds == y.bx_lds &&
+                   x.ovl_lds == y.ovl_lds && x.bx_upt == y.bx_upt && x.bx_lds == y.bx_lds && x.bx_w2 == y.bx_w2 &&
                    x.tiled_tr == y.tiled_tr && x.lg_tr == y.lg_tr && x.lg_jr == y.lg_jr && x.lg_tq == y.lg_tq;
         };
         size_t o = 0;
@@ -1480,6 +1502,10 @@ int psn_lk_debug_set_variant(psn_lk_ctx *c, int key, int value) {
     case PSN_LK_VARIANT_LG_JR: c->lg_jr = value != 0; return PSN_LK_OK;
     case PSN_LK_VARIANT_ST_OVL: c->st_ovl = value != 0; return PSN_LK_OK;
     case PSN_LK_VARIANT_POISON_LDS: c->poison_lds = value != 0; return PSN_LK_OK;
+    case PSN_LK_VARIANT_BX_WAVES:
+        if (value != 0 && value != 2 && value != 4) return PSN_LK_ERR_ARG;
+        c->bx_waves = value;
+        return PSN_LK_OK;
     default: return PSN_LK_ERR_ARG;
     }
 }

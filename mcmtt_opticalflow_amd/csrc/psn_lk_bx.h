@@ -352,6 +352,20 @@ __device__ __forceinline__ void bx_unit(const uint32_t *P32, int PM, int sh, int
     YPk[1] = pack_w(iy[2], iy[3]);
 }
 
+// Quarter-wave tiles (the two-wave build of lk_kernel_bx): one output of the 4 x 4
+// transpose of registers r0..r3 over the wave's four 16-lane rows -- lane (row r,
+// i) gets r_r of lane (row TQ, i). v_permlane32_swap exchanges the upper half of
+// its first operand with the lower half of its second (rows 2, 3 <-> rows 0, 1),
+// v_permlane16_swap the odd rows of its first with the even rows of its second:
+// the halves pick TQ's row pair, the rows TQ's row of the pair.
+template <int TQ>
+__device__ __forceinline__ unsigned bx_qpick(unsigned r0, unsigned r1, unsigned r2, unsigned r3) {
+    auto s02 = __builtin_amdgcn_permlane32_swap(r0, r2, false, false);
+    auto s13 = __builtin_amdgcn_permlane32_swap(r1, r3, false, false);
+    auto t = __builtin_amdgcn_permlane16_swap(s02[TQ >> 1], s13[TQ >> 1], false, false);
+    return t[TQ & 1];
+}
+
 // Ordered float sum of a zero-padded LDS chain (16-B aligned, ceil(len/16)
 // blocks of 16 floats; +0 pads leave an integer-valued sum unchanged) onto acc,
 // with one block in flight while one is summed: the LDS latency (~100 cycles)

@@ -252,6 +252,13 @@ struct LkStLayout {
 // bx_jrp(w)) | a union of the level's I patch (bytes, rows of bx_pm(w) dwords)
 // and the row-tiled float chain planes of the ordered-sum fallbacks.
 constexpr int kBxNT = 256;
+// The two-wave build (lk_kernel_bx<8, true, kBxNT2>): a no-tail window of at most
+// kBxNT2 * 8 units in a workgroup of two waves, 8 units per thread at 168 VGPRs
+// (three waves per SIMD: six workgroups per CU by registers), with fallback tiles
+// of kBxTile2 threads so that six workgroups fit the CU's LDS as well.
+constexpr int kBxNT2 = 128;
+constexpr int kBxUPT2 = 8;
+constexpr int kBxTile = 32, kBxTile2 = 16;  // threads per fallback tile granule
 constexpr int kBxMaxUPT = 16;
 constexpr int kBxRecInts = 8 * 15 + 4;                 // per wave and chain: {total, max, min prefix, -} at lanes 31 and 63; term flag
 constexpr int kBxXInts = 2 * 4 * kBxRecInts;           // two parities x 4 waves
@@ -263,15 +270,25 @@ constexpr int kBxLdsTarget = 53 * 1024;  // three workgroups per CU
 // 4-unit build fits 128 VGPRs, so four per CU when the LDS plan allows it; the
 // builds whose registers do not fit 168 VGPRs at three per CU (12 units, and 10
 // units with the scalar-tail chain: 8-33 spilled VGPRs; 16 units) run two per CU
-__host__ __device__ constexpr int bx_occupancy(int upt, bool notail) {
-    return upt <= 4 ? 4 : (upt >= 12 || (!notail && upt >= 10)) ? 2 : 3;
+// (the two-wave build: 3 waves per SIMD x 4 SIMDs / 2 waves = six per CU)
+__host__ __device__ constexpr int bx_occupancy(int upt, bool notail, int nt = kBxNT) {
+    return nt == kBxNT2 ? 6 : upt <= 4 ? 4 : (upt >= 12 || (!notail && upt >= 10)) ? 2 : 3;
 }
-__host__ __device__ constexpr int bx_lds_target(int upt, bool notail) {
-    return bx_occupancy(upt, notail) == 4 ? 40 * 1024 : bx_occupancy(upt, notail) == 3 ? kBxLdsTarget : kBxMaxLds2;
+// waves per SIMD the build is held to (its __launch_bounds__)
+__host__ __device__ constexpr int bx_waves_per_simd(int upt, bool notail, int nt = kBxNT) {
+    return bx_occupancy(upt, notail, nt) * (nt / 64) / 4;
 }
-// the largest LDS plan of a lk_kernel_bx<upt, notail> launch
-__host__ __device__ constexpr int bx_max_lds(int upt, bool notail) {
-    return bx_occupancy(upt, notail) == 2 ? kBxMaxLds2 : kBxMaxLds;
+constexpr int kBxLdsTarget6 = 160 * 1024 / 6;  // 27,306 B: six workgroups per CU
+__host__ __device__ constexpr int bx_lds_target(int upt, bool notail, int nt = kBxNT) {
+    return nt == kBxNT2                        ? kBxLdsTarget6
+           : bx_occupancy(upt, notail) == 4 ? 40 * 1024
+           : bx_occupancy(upt, notail) == 3 ? kBxLdsTarget
+                                            : kBxMaxLds2;
+}
+// the largest LDS plan of a lk_kernel_bx<upt, notail, nt> launch (the two-wave
+// build only takes windows whose plan keeps six per CU)
+__host__ __device__ constexpr int bx_max_lds(int upt, bool notail, int nt = kBxNT) {
+    return nt == kBxNT2 ? kBxLdsTarget6 : bx_occupancy(upt, notail) == 2 ? kBxMaxLds2 : kBxMaxLds;
 }
 __host__ __device__ inline int bx_qw(int w) { return (w + 3) >> 2; }
 __host__ __device__ inline int bx_pm(int w) { return bx_qw(w) + 2; }      // I patch dwords per row
@@ -281,20 +298,28 @@ __host__ __device__ inline int bx_round4(int x) { return (x + 3) & ~3; }
 // region stride of 4 (mod 16) floats the chain lanes' 16-B reads of one plane
 // fall into different 4-bank groups (conflict-free).
 __host__ __device__ inline int bx_region(int n) { return ((n + 15) & ~15) + 4; }
-// Fallback tiles are half-wave unit ranges (32 threads x UPT units): one plane
-// (4 SSE2 lane regions + the tail region) holds at most 4*32*UPT terms + padding.
-__host__ __device__ inline int bx_pc(int upt) { return 128 * upt + 96; }
+// Fallback tiles are unit ranges of `tile` threads x UPT units (half waves; quarter
+// waves in the two-wave build): one plane (4 SSE2 lane regions + the tail region)
+// holds at most 4*tile*UPT terms + padding.
+__host__ __device__ inline int bx_pc(int upt, int tile = kBxTile) { return 4 * tile * upt + 96; }
 struct BxLayout {
     int jr, un, pb, total;
-    __host__ __device__ BxLayout(int w, int h, int upt, int hw = 1) {
+    __host__ __device__ BxLayout(int w, int h, int upt, int hw = 1, int tile = kBxTile) {
         jr = align16(kBxScrBytes);
         un = jr + align16(st_jreg_h(h) * bx_jrp(w));
         const int pim = align16((h + 3) * 4 * bx_pm(w));
-        const int planes = 24 * bx_pc(upt) * hw;  // tiles of hw half waves, 2 buffers x (A: 3, b: 2) planes
+        const int planes = 24 * bx_pc(upt, tile) * hw;  // tiles of hw granules, 2 buffers x (A: 3, b: 2) planes
         pb = pim > planes ? pim : planes;
         total = un + pb + 1024;  // slack: the chain sums read up to 5 blocks past a chain (discarded)
     }
 };
+// The two-wave build takes a no-tail window (SSE2 order, w % 8 == 0) of at most
+// kBxNT2 * kBxUPT2 units whose LDS plan with kBxTile2-thread tiles keeps six
+// workgroups per CU.
+__host__ __device__ inline bool bx_two_wave_fits(int w, int h, bool notail) {
+    return notail && (long)h * bx_qw(w) <= kBxNT2 * kBxUPT2 &&
+           BxLayout(w, h, kBxUPT2, 1, kBxTile2).total <= kBxLdsTarget6;
+}
 // Row tiles of the (rare) err chain fallback: one row-major plane.
 inline int bx_err_rows(int w, int h, int pb) {
     for (int t = h; t >= 1; t--)
@@ -417,8 +442,10 @@ hipError_t launch_lk_st(const LkLaunchArgs &a, int total_wgs, int nt, int ept, i
                         hipStream_t s);
 // Box-window kernel with UPT units per thread (4, 8, 10, 12 or 16).
 // notail: every query of the launch sums in the SSE2 order with width % 8 == 0
-// (no scalar-tail chain: a build without its per-pixel bookkeeping)
-hipError_t launch_lk_bx(const LkLaunchArgs &a, int total_wgs, int upt, bool notail, int lds_bytes, hipStream_t s);
+// (no scalar-tail chain: a build without its per-pixel bookkeeping); nt: the
+// workgroup size (kBxNT, or kBxNT2 for the two-wave build <8, true>)
+hipError_t launch_lk_bx(const LkLaunchArgs &a, int total_wgs, int upt, bool notail, int nt, int lds_bytes,
+                        hipStream_t s);
 // Large-window kernel (psn_lk_large.hip): `grid` workgroups over a.lk_wgs points.
 hipError_t launch_lk_lg(const LkLaunchArgs &a, int grid, int lds_bytes, int tq, hipStream_t s);
 hipError_t lg_kernels_init();

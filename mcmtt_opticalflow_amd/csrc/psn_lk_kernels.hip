@@ -1867,7 +1867,8 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
 // ---------------------------------------------------------------------------
 // lk_kernel_bx -- box windows (Tracker2D: (int)box.w x (int)box.w backward,
 // PSNWhere_Tracker2D.cpp:776-782; box w x h forward, :871-877) above the
-// single-tile kernel's size. Workgroup = one point, 4 waves. The window is cut
+// single-tile kernel's size. Workgroup = one point, 4 waves (2 in the two-wave
+// build, NT = kBxNT2). The window is cut
 // into units of 4 pixels (row y, quad q) in row-major order and thread t owns
 // the CONTIGUOUS units [t*UPT, t*UPT + UPT): for every SSE2 lane chain (x & 3,
 // pixels below the 8- resp. 4-pixel-step bound) and the scalar tail chain the
@@ -1886,11 +1887,18 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
 // Diagnostic phase clocks (PSN_LK_STAMPS, psn_lk_stamps.h; thread 0's view):
 // accumulated s_memtime ticks per phase in bx_acc, written as stamps[wg][0..15]
 // at the end.
-template <int UPT, bool NOTAIL>
-__global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx(LkLaunchArgs A) {
+// NT: the workgroup size. kBxNT2 is the two-wave build (QT below): the same
+// kernel with two waves' records, err partials and staging strides, and fallback
+// tiles of a quarter wave (kBxTile2 threads), each written by its whole wave.
+template <int UPT, bool NOTAIL, int NT = kBxNT>
+__global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_kernel_bx(LkLaunchArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     static_assert(UPT % 2 == 0, "units are processed in pairs");
-    constexpr int NT = kBxNT;
+    static_assert(NT == kBxNT || (NT == kBxNT2 && NOTAIL && UPT == kBxUPT2), "the two-wave build is <8, true>");
+    constexpr int NW = NT / 64;             // waves
+    constexpr bool QT = NT == kBxNT2;       // quarter-wave fallback tiles
+    constexpr int TG = QT ? kBxTile2 : kBxTile;  // threads per fallback tile granule
+    constexpr int TPH = 32 / TG;            // tiles per half wave (exactness is decided per half wave)
     const int tid = threadIdx.x, lane = tid & 63;
     if (A.poison_lds) lds_poison<NT>(smem, A.poison_lds);
     const int g = xcd_remap((int)blockIdx.x, (int)gridDim.x);
@@ -1906,7 +1914,7 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
     const int nqB = sse ? (w / 8) * 2 : 0, n8 = 4 * nqB, tB = w - n8;   // b: 8-pixel steps
     const int nqA = sse ? w / 4 : 0, nA4 = 4 * nqA, tA = w - nA4;        // A: 4-pixel steps
     const int PM = bx_pm(w), JRW = st_jreg_w(w), JRH = st_jreg_h(h), JRP = bx_jrp(w), JRP4 = JRP >> 2;
-    const BxLayout lay(w, h, UPT);
+    const BxLayout lay(w, h, UPT, 1, TG);
     int *X = (int *)smem;                      // chain-check records, two parities
     float *RS = (float *)(X + kBxXInts);       // serial-chain results (wave 0 -> all)
     int *EP = (int *)(RS + 16);                // err partial sums per wave
@@ -1915,6 +1923,14 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
     // then reported failed, see the result writes)
     volatile int *FLG = (volatile int *)(RS + 24);
     if (threadIdx.x < 7) FLG[threadIdx.x] = threadIdx.x < 6 ? -1 : 0;  // ordered by the first level barrier
+    if constexpr (NW < 4) {
+        // the records of the absent waves, once per parity (no wave ever writes
+        // them): totals 0, verdict "none" -- bx_check / bx_eval read four waves
+        if (tid < kBxRecInts) {
+            const int v = tid < kBxHalfRec ? 0 : 8;
+            if ((tid & 3) >= NW) X[tid] = X[4 * kBxRecInts + tid] = v;
+        }
+    }
     int fb_epoch = 0;
     uint8_t *JR = smem + lay.jr;
     const uint32_t *JR32 = (const uint32_t *)JR;
@@ -2144,13 +2160,13 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 // here, not hoisted to the kernel start and spilled across the loops
                 int ftid = (int)threadIdx.x;
                 asm volatile("" : "+v"(ftid));
-                const int HW = Q.bx_hw, PCA = 3 * bx_pc(UPT) * HW;
+                const int HW = QT ? 1 : Q.bx_hw, PCA = 3 * bx_pc(UPT, TG) * HW;
                 const bool chl = ftid < 15;  // wave 0: its tiles are written first, so it rarely writes while it sums
                 const int cl = chl ? ftid : 0, cs = cl / 5, cc = cl - 5 * cs;
                 float acc = (float)base0;  // |base0| <= 2^24: exact
-                const int g_last = (U - 1) / (32 * UPT);
+                const int g_last = (U - 1) / (TG * UPT), g_first = h0 * TPH;
                 auto geoA = [&](int g, int &sa, int &ta, int &nsse, int &ntail) {
-                    const int ua = 32 * UPT * g, ub = min(ua + 32 * UPT * HW, U);
+                    const int ua = TG * UPT * g, ub = min(ua + TG * UPT * HW, U);
                     sa = (ua / QW) * nqA + min(ua % QW, nqA);
                     ta = (ua / QW) * tA + min(max(4 * (ua % QW) - nA4, 0), tA);
                     nsse = (ub / QW) * nqA + min(ub % QW, nqA) - sa;
@@ -2178,7 +2194,7 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 };
                 // half-wave tiles: the whole wave writes one (as the b fallback's write_tile)
                 constexpr int K1 = UPT / 2;
-                const bool split = HW == 1 && (UPT & 1) == 0;
+                const bool split = !QT && HW == 1 && (UPT & 1) == 0;
                 auto swp = [](unsigned a, unsigned b, bool first) {
                     auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
                     return first ? r[0] : r[1];
@@ -2205,6 +2221,36 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                         if (ub + k < U) {
                             asm volatile("" : "+v"(xp[0]), "+v"(xp[1]), "+v"(yp[0]), "+v"(yp[1]));
                             float *d1 = buf + rel + k;
+#pragma unroll
+                            for (int i = 0; i < 4; i++) {
+                                const int gx = (i & 1) ? hi16(xp[i >> 1]) : lo16(xp[i >> 1]);
+                                const int gy = (i & 1) ? hi16(yp[i >> 1]) : lo16(yp[i >> 1]);
+                                d1[i * S] = (float)__mul24(gx, gx);
+                                d1[i * S + P] = (float)__mul24(gx, gy);
+                                d1[i * S + 2 * P] = (float)__mul24(gy, gy);
+                            }
+                        }
+                    }
+                };
+                // two-wave build, quarter-wave tiles: the tile's wave writes it with all
+                // four rows -- row r takes the units 2r, 2r + 1 of the tile's threads
+                // (bx_qpick over the unit pairs' registers), the quarter picked at
+                // compile time; slots from the unit's index in the tile
+                auto writeA_q = [&](int g, float *buf, auto tqT) __attribute__((always_inline)) {
+                    constexpr int TQ = decltype(tqT)::value;
+                    int sa, ta, nsse, ntail;
+                    geoA(g, sa, ta, nsse, ntail);
+                    const int S = bx_region(nsse), P = 4 * S + bx_region(ntail);
+                    const int rel = (ftid & 15) * UPT + 2 * ((ftid >> 4) & 3), ub = TG * UPT * g + rel;
+#pragma unroll
+                    for (int j = 0; j < 2; j++) {
+                        unsigned xp[2] = {bx_qpick<TQ>(XP[j][0], XP[2 + j][0], XP[4 + j][0], XP[6 + j][0]),
+                                          bx_qpick<TQ>(XP[j][1], XP[2 + j][1], XP[4 + j][1], XP[6 + j][1])};
+                        unsigned yp[2] = {bx_qpick<TQ>(YP[j][0], YP[2 + j][0], YP[4 + j][0], YP[6 + j][0]),
+                                          bx_qpick<TQ>(YP[j][1], YP[2 + j][1], YP[4 + j][1], YP[6 + j][1])};
+                        if (ub + j < U) {
+                            asm volatile("" : "+v"(xp[0]), "+v"(xp[1]), "+v"(yp[0]), "+v"(yp[1]));
+                            float *d1 = buf + rel + j;
 #pragma unroll
                             for (int i = 0; i < 4; i++) {
                                 const int gx = (i & 1) ? hi16(xp[i >> 1]) : lo16(xp[i >> 1]);
@@ -2279,6 +2325,18 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                         }
                     }
                 };
+                // the tile writer of the build. (The two-wave build's is always inlined, and
+                // generic so that only that build instantiates it: as a call its four
+                // quarter bodies would keep the by-reference captures in scratch.)
+                auto writeA_qt = [&](int g, float *buf, auto) __attribute__((always_inline)) {
+                    if ((ftid >> 6) != (g >> 2)) return;
+                    switch (g & 3) {
+                        case 0: writeA_q(g, buf, std::integral_constant<int, 0>()); break;
+                        case 1: writeA_q(g, buf, std::integral_constant<int, 1>()); break;
+                        case 2: writeA_q(g, buf, std::integral_constant<int, 2>()); break;
+                        default: writeA_q(g, buf, std::integral_constant<int, 3>()); break;
+                    }
+                };
                 auto padA = [&](int g, float *buf) {  // chain lanes: zero their region's pad
                     if (!chl) return;
                     int sa, ta, nsse, ntail;
@@ -2289,12 +2347,20 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                     for (int i = len; i < ((len + 15) & ~15); i++) rg[i] = 0.f;
                 };
                 // the I patch under PL was consumed before the publish barrier
-                writeA(h0, PL);
-                padA(h0, PL);
+                if constexpr (QT)
+                    writeA_qt(g_first, PL, 0);
+                else
+                    writeA(g_first, PL);
+                padA(g_first, PL);
                 __syncthreads();
-                for (int g = h0, t = 0; g <= g_last; g += HW, t ^= 1) {
+                for (int g = g_first, t = 0; g <= g_last; g += HW, t ^= 1) {
                     float *cur = PL + t * PCA, *nxt = PL + (t ^ 1) * PCA;
-                    if (g + HW <= g_last) writeA(g + HW, nxt);
+                    if (g + HW <= g_last) {
+                        if constexpr (QT)
+                            writeA_qt(g + HW, nxt, 0);
+                        else
+                            writeA(g + HW, nxt);
+                    }
                     if ((ftid >> 6) == 0) {
                         int sa, ta, nsse, ntail;
                         geoA(g, sa, ta, nsse, ntail);
@@ -2365,6 +2431,8 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 // scalars (the J region's constant offset stays inside them: one
                 // SDWA add per row and unit, not two adds and a constant)
                 unsigned jo0 = (unsigned)((const uint8_t *)(JR32 + oy * JRP4 + (ox >> 2)) - smem);
+                // (the two-wave build: the compiler does not prove the offset uniform; it is)
+                if constexpr (QT) jo0 = (unsigned)__builtin_amdgcn_readfirstlane((int)jo0);
                 unsigned jo1 = jo0 + 4u * (unsigned)JRP4;
                 asm volatile("" : "+s"(jo0), "+s"(jo1));
                 // units in pairs (UPT is even): each chain takes its two terms by
@@ -2500,13 +2568,13 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 // thread roles from an opaque copy of the thread id (see the A fallback)
                 int ftid = (int)threadIdx.x;
                 asm volatile("" : "+v"(ftid));
-                const int HW = Q.bx_hw, PC = bx_pc(UPT) * HW;
+                const int HW = QT ? 1 : Q.bx_hw, PC = bx_pc(UPT, TG) * HW;
                 const bool chl = ftid < 10;  // wave 0 (as in the A fallback)
                 const int cl = chl ? ftid : 0, cs = cl / 5, cc = cl - 5 * cs;
                 float acc = (float)base0;
-                const int g_last = (U - 1) / (32 * UPT);
+                const int g_last = (U - 1) / (TG * UPT), g_first = h0 * TPH;
                 auto tile_geo = [&](int g, int &sa, int &ta, int &nsse, int &ntail) {
-                    const int ua = 32 * UPT * g, ub = min(ua + 32 * UPT * HW, U);
+                    const int ua = TG * UPT * g, ub = min(ua + TG * UPT * HW, U);
                     sa = (ua / QW) * nqB + min(ua % QW, nqB);
                     ta = (ua / QW) * tB + min(max(4 * (ua % QW) - n8, 0), tB);
                     nsse = (ub / QW) * nqB + min(ub % QW, nqB) - sa;
@@ -2538,10 +2606,56 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 // lane l + 32's unit K1 + k there and its unit k on lane l (an upper-half
                 // tile): both halves run one instruction stream.
                 constexpr int K1 = UPT / 2;
-                const bool split = HW == 1 && (UPT & 1) == 0;
+                const bool split = !QT && HW == 1 && (UPT & 1) == 0;
                 auto swp = [](unsigned a, unsigned b, bool first) {
                     auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
                     return first ? r[0] : r[1];
+                };
+                // two-wave build, quarter-wave tiles (as the A fallback's writeA_q): the
+                // unit pair's packed J offsets travel like its window values
+                auto write_tile_q = [&](int g, float *buf, auto tqT) __attribute__((always_inline)) {
+                    constexpr int TQ = decltype(tqT)::value;
+                    const int zf = opaque256();
+                    const unsigned qo0 = (unsigned)((const uint8_t *)(JR32 + oy * JRP4 + (ox >> 2)) - smem);
+                    const unsigned qo1 = qo0 + 4u * (unsigned)JRP4;
+                    int sa, ta, nsse, ntail;
+                    tile_geo(g, sa, ta, nsse, ntail);
+                    const int S = bx_region(nsse), P = 4 * S + bx_region(ntail);
+                    const int rel = (ftid & 15) * UPT + 2 * ((ftid >> 4) & 3), ub = TG * UPT * g + rel;
+                    constexpr int U2 = UPT > 4 ? 2 : 0, U3 = UPT > 6 ? 3 : 0;  // (only this build instantiates the body)
+                    const unsigned ubp = bx_qpick<TQ>(UB[0], UB[1], UB[U2], UB[U3]);
+#pragma unroll
+                    for (int j = 0; j < 2; j++) {
+                        const unsigned ip[2] = {bx_qpick<TQ>(IP[j][0], IP[2 + j][0], IP[4 + j][0], IP[6 + j][0]),
+                                                bx_qpick<TQ>(IP[j][1], IP[2 + j][1], IP[4 + j][1], IP[6 + j][1])};
+                        const unsigned xp[2] = {bx_qpick<TQ>(XP[j][0], XP[2 + j][0], XP[4 + j][0], XP[6 + j][0]),
+                                                bx_qpick<TQ>(XP[j][1], XP[2 + j][1], XP[4 + j][1], XP[6 + j][1])};
+                        const unsigned yp[2] = {bx_qpick<TQ>(YP[j][0], YP[2 + j][0], YP[4 + j][0], YP[6 + j][0]),
+                                                bx_qpick<TQ>(YP[j][1], YP[2 + j][1], YP[4 + j][1], YP[6 + j][1])};
+                        const unsigned off = j ? ubp >> 16 : ubp & 0xffffu;
+                        if (ub + j < U) {
+                            int d[4];
+                            bx_diffs2((const uint32_t *)(smem + qo0 + off), (const uint32_t *)(smem + qo1 + off), W0, W1, s0,
+                                      s1, s2, s3, ip, d, zf);
+                            float *d1 = buf + rel + j;
+#pragma unroll
+                            for (int i = 0; i < 4; i++) {
+                                const int gx = (i & 1) ? hi16(xp[i >> 1]) : lo16(xp[i >> 1]);
+                                const int gy = (i & 1) ? hi16(yp[i >> 1]) : lo16(yp[i >> 1]);
+                                d1[i * S] = (float)__mul24(d[i], gx);
+                                d1[i * S + P] = (float)__mul24(d[i], gy);
+                            }
+                        }
+                    }
+                };
+                auto write_tile_qt = [&](int g, float *buf, auto) __attribute__((always_inline)) {
+                    if ((ftid >> 6) != (g >> 2)) return;
+                    switch (g & 3) {
+                        case 0: write_tile_q(g, buf, std::integral_constant<int, 0>()); break;
+                        case 1: write_tile_q(g, buf, std::integral_constant<int, 1>()); break;
+                        case 2: write_tile_q(g, buf, std::integral_constant<int, 2>()); break;
+                        default: write_tile_q(g, buf, std::integral_constant<int, 3>()); break;
+                    }
                 };
                 auto write_tile = [&](int g, float *buf) {
                     const int zf = opaque256();  // per tile: no diff constants hoisted out of the tile loop
@@ -2614,6 +2728,7 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 // index in the tile (every quad is an SSE2 quad, every pixel inside the
                 // window); the tile's half picked at compile time (no select per value)
                 unsigned fo0 = (unsigned)((const uint8_t *)(JR32 + oy * JRP4 + (ox >> 2)) - smem);
+                if constexpr (QT) fo0 = (unsigned)__builtin_amdgcn_readfirstlane((int)fo0);
                 unsigned fo1 = fo0 + 4u * (unsigned)JRP4;
                 asm volatile("" : "+s"(fo0), "+s"(fo1));
                 auto write_tile_nt = [&](int g, float *buf, auto lowerT) {
@@ -2718,13 +2833,21 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
                 } else
 #endif
                 {
-                write_tile(h0, PL);
-                pad_tile(h0, PL);
+                if constexpr (QT)
+                    write_tile_qt(g_first, PL, 0);
+                else
+                    write_tile(g_first, PL);
+                pad_tile(g_first, PL);
                 __syncthreads();
                 PSN_PH_MARK(bx_acc, bx_t, 6);  // serial b: first tile's products
-                for (int g = h0, t = 0; g <= g_last; g += HW, t ^= 1) {  // tile = half waves g .. g+HW-1
+                for (int g = g_first, t = 0; g <= g_last; g += HW, t ^= 1) {  // tile = granules g .. g+HW-1
                     float *cur = PL + t * 2 * PC, *nxt = PL + (t ^ 1) * 2 * PC;
-                    if (g + HW <= g_last) write_tile(g + HW, nxt);
+                    if (g + HW <= g_last) {
+                        if constexpr (QT)
+                            write_tile_qt(g + HW, nxt, 0);
+                        else
+                            write_tile(g + HW, nxt);
+                    }
 #ifdef PSN_LK_STAMPS
                     unsigned long long tc0, tc1, tc2;
                     PSN_CLK_ORDERED(tc0);
@@ -2814,7 +2937,9 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
             e = (unsigned)wave_sum((int)e);  // <= 64 * 48 * 8160 < 2^31
             if (lane == 0) EP[tid >> 6] = (int)e;
             __syncthreads();
-            const unsigned et = (unsigned)EP[0] + (unsigned)EP[1] + (unsigned)EP[2] + (unsigned)EP[3];
+            unsigned et = 0;
+#pragma unroll
+            for (int wv = 0; wv < NW; wv++) et += (unsigned)EP[wv];
             float errval;
             if (et <= (unsigned)kExact) {
                 errval = (float)et;  // every partial sum of errval += |diff| is an exact integer
@@ -2886,10 +3011,11 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
 // The instantiations of each kernel family, written ONCE: the launch dispatch and
 // the dynamic-LDS attribute loop of lk_kernels_init are both generated from these
 // lists, so a variant cannot launch without its attribute.
-// lk_kernel_bx: X(UPT units per thread, NOTAIL).
-#define PSN_BX_KERNELS(X)                                         \
-    X(4, true) X(4, false) X(8, true) X(8, false) X(10, true)     \
-    X(10, false) X(12, true) X(12, false) X(16, true) X(16, false)
+// lk_kernel_bx: X(UPT units per thread, NOTAIL, NT workgroup size).
+#define PSN_BX_KERNELS(X)                                                              \
+    X(4, true, kBxNT) X(4, false, kBxNT) X(8, true, kBxNT) X(8, false, kBxNT)          \
+    X(10, true, kBxNT) X(10, false, kBxNT) X(12, true, kBxNT) X(12, false, kBxNT)      \
+    X(16, true, kBxNT) X(16, false, kBxNT) X(kBxUPT2, true, kBxNT2)
 // lk_kernel_st: X(NT workgroup size, EPT window pixels per thread, E one-wave
 // rows per lane (0: multi-wave iterations), OCC workgroups per CU the build is
 // held to). The OCC 3 builds are the one-wave kernels held to 168 VGPRs: three
@@ -2900,13 +3026,14 @@ __global__ __launch_bounds__(kBxNT, bx_occupancy(UPT, NOTAIL)) void lk_kernel_bx
     X(256, 4, 8, 1) X(256, 2, 16, 1) X(256, 4, 16, 1) X(256, 4, 0, 1) X(256, 2, 4, 3)     \
     X(256, 2, 7, 3) X(256, 2, 8, 3)
 
-hipError_t launch_lk_bx(const LkLaunchArgs &a, int total_wgs, int upt, bool notail, int lds_bytes, hipStream_t s) {
+hipError_t launch_lk_bx(const LkLaunchArgs &a, int total_wgs, int upt, bool notail, int nt, int lds_bytes,
+                        hipStream_t s) {
     if (total_wgs <= 0) return hipSuccess;
-    const dim3 grid(total_wgs), block(kBxNT);
-#define PSN_BX_LAUNCH(U, NOTAIL)                                                         \
-    if (upt == U && notail == NOTAIL) {                                                  \
-        hipLaunchKernelGGL((lk_kernel_bx<U, NOTAIL>), grid, block, lds_bytes, s, a);     \
-        return hipGetLastError();                                                        \
+    const dim3 grid(total_wgs);
+#define PSN_BX_LAUNCH(U, NOTAIL, NT)                                                            \
+    if (upt == U && notail == NOTAIL && nt == NT) {                                             \
+        hipLaunchKernelGGL((lk_kernel_bx<U, NOTAIL, NT>), grid, dim3(NT), lds_bytes, s, a);     \
+        return hipGetLastError();                                                               \
     }
     PSN_BX_KERNELS(PSN_BX_LAUNCH)
 #undef PSN_BX_LAUNCH
@@ -2940,7 +3067,7 @@ hipError_t launch_lk(const LkLaunchArgs &a, int total_wgs, int threads, int lds_
 
 hipError_t lk_kernels_init() {
     const int max_lds = 160 * 1024;
-#define PSN_BX_FN(U, NOTAIL) (const void *)lk_kernel_bx<U, NOTAIL>,
+#define PSN_BX_FN(U, NOTAIL, NT) (const void *)lk_kernel_bx<U, NOTAIL, NT>,
 #define PSN_ST_FN(NT, EPT, E, OCC) (const void *)lk_kernel_st<NT, EPT, E, OCC>,
     const void *fns[] = {(const void *)lk_kernel<64>, (const void *)lk_kernel<128>, (const void *)lk_kernel<256>,
                          PSN_ST_KERNELS(PSN_ST_FN) PSN_BX_KERNELS(PSN_BX_FN) (const void *)pyramid_kernel};

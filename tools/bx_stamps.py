@@ -7,6 +7,8 @@ Prints per-workgroup mean / slowest cycles per phase (s_memtime ticks, thread
 0's view) and the serial-chain fraction of the iterations.
 
   WIN=64 WINH=160 NPTS=630 python tools/bx_stamps.py
+  WIN=64 WINH=64 NPTS=2048 VARIANTS=bx_waves=4 python tools/bx_stamps.py   # the four-wave build; bx_waves=2:
+                                                                            # the two-wave lk_kernel_bx<8, true, 128>
 """
 import json
 import os
@@ -33,7 +35,8 @@ def main():
     pts = sc.points_at(1)
     L = _lib.load(_lib.STAMPS_LIB_PATH)
     st = hiprt.DeviceBuffer(npts * 64 * 8)
-    with lk.LKContext(1920, 1080, ring_slots=2, max_level_cap=3) as ctx:
+    variants = {k: int(v) for k, v in (kv.split("=") for kv in os.environ.get("VARIANTS", "").split(",") if kv)}
+    with lk.LKContext(1920, 1080, ring_slots=2, max_level_cap=3, variants=variants) as ctx:
         ctx.push_frame(0, f0)
         ctx.push_frame(1, f1)
         rc = L.psn_lk_debug_set_stamps(ctx.handle, st.addr)
@@ -41,12 +44,16 @@ def main():
         q = lk.make_query(1, 0, 0, npts, lk.make_params((w, h), 3))
         for _ in range(3):
             ctx.track([q], pts)
+        L.psn_lk_enable_timing(ctx.handle, 2, 1)
+        ctx.track([q], pts)
+        ctx.sync()
+        kernels = sorted({_lib.kernel_of_tag(t) for _, t in _lib.timing_launches(L, ctx.handle, 2)})
         s = st.to_array((npts, 64), np.uint64).astype(np.int64)
     tot = s[:, 15]
     slow = int(np.argmax(tot))
     ph = s[:, :9].copy()
     ph[:, 5] += s[:, 9]  # slot 9 splits b_publish_eval: publish (9) + barrier and eval (5)
-    out = {"window": [w, h], "points": npts, "wg_cycles_mean": float(tot.mean()), "wg_cycles_max": int(tot.max()),
+    out = {"window": [w, h], "points": npts, "variants": variants, "kernel": ",".join(kernels), "wg_cycles_mean": float(tot.mean()), "wg_cycles_max": int(tot.max()),
            "iterations_mean": float(s[:, 10].mean()), "iterations_max": int(s[:, 10].max()),
            "serial_b_fraction": round(float(s[:, 11].sum() / max(s[:, 10].sum(), 1)), 3),
            "mean": {k: round(float(v), 1) for k, v in zip(PHASES, ph.mean(0))},

@@ -8,6 +8,8 @@ the median / mean over `--reps` launches and a checksum of the outputs (the
 same checksum across builds = the same results).
 
   python tools/bx_time.py --reps 40
+  python tools/bx_time.py --shapes 64x64 --variants bx_waves=4   # the four-wave build of a two-wave window
+  python tools/bx_time.py --shapes 64x64 --variants bx_waves=2   # lk_kernel_bx<8, true, 128>
 """
 import argparse
 import hashlib
@@ -48,11 +50,14 @@ def main():
             L.psn_lk_enable_timing(ctx.handle, args.reps + 1, 1)
             for _ in range(args.reps):
                 res = ctx.track([q], pts)
-            ms = np.array([m for m, _ in _lib.timing_launches(L, ctx.handle, args.reps + 1)])
+            timed = _lib.timing_launches(L, ctx.handle, args.reps + 1)
+            ms = np.array([m for m, _ in timed])
+            kernels = sorted({_lib.kernel_of_tag(t) for _, t in timed})
             L.psn_lk_enable_timing(ctx.handle, 0, 1)
             dig = hashlib.sha1(b"".join(np.ascontiguousarray(a).tobytes() for a in res)).hexdigest()[:16]
             out[shape] = {"median_us": round(1e3 * float(np.median(ms)), 1), "mean_us": round(1e3 * float(ms.mean()), 1),
-                          "min_us": round(1e3 * float(ms.min()), 1), "launches": int(ms.size), "out_sha": dig}
+                          "min_us": round(1e3 * float(ms.min()), 1), "launches": int(ms.size), "out_sha": dig,
+                          "kernel": ",".join(kernels)}
     print(json.dumps(out))
 
 

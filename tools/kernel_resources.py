@@ -52,9 +52,20 @@ def kernels(lib):
     return out
 
 
+def pretty(mangled):
+    """The box kernel's builds by the name _lib.kernel_of_tag gives their launches:
+    lk_kernel_bx<8, true, 128> for _ZN3psn12lk_kernel_bxILi8ELb1ELi128EEEvNS_12LkLaunchArgsE (the
+    builds of 256 threads drop the default size); other kernels keep the mangled name."""
+    m = re.search(r"lk_kernel_bxILi(\d+)ELb([01])ELi(\d+)E", mangled)
+    if not m:
+        return mangled
+    upt, notail, nt = int(m.group(1)), m.group(2) == "1", int(m.group(3))
+    return f"lk_kernel_bx<{upt}, {'true' if notail else 'false'}" + (">" if nt == 256 else f", {nt}>")
+
+
 if __name__ == "__main__":
     lib = sys.argv[1] if len(sys.argv) > 1 else "mcmtt_opticalflow_amd/lib/libpsn_lk.so"
     rx = sys.argv[2] if len(sys.argv) > 2 else "lk_kernel"
     for n, r in sorted(kernels(lib).items()):
-        if re.search(rx, n):
-            print(f"{n:56s} vgpr {r['vgpr']:>4s} spill {r['vgpr_spill']:>3s} scratch {r['scratch']:>4s}")
+        if re.search(rx, n) or re.search(rx, pretty(n)):
+            print(f"{pretty(n):56s} vgpr {r['vgpr']:>4s} spill {r['vgpr_spill']:>3s} scratch {r['scratch']:>4s}")

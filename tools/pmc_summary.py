@@ -14,6 +14,7 @@ import csv
 import glob
 import json
 import os
+import re
 import sys
 from collections import defaultdict
 
@@ -31,9 +32,12 @@ def load(d, counter):
 
 def short(name):
     # the box-window kernel has one instantiation per unit count: keep them apart
+    # (by the name _lib.kernel_of_tag and kernel_resources.pretty give them: the
+    # builds of 256 threads drop the default workgroup size, the two-wave build
+    # keeps its 128 -- "lk_kernel_bx<10, true>", "lk_kernel_bx<8, true, 128>")
     i = name.find("lk_kernel_bx<")
     if i >= 0:
-        return name[i:name.index(">", i) + 1]
+        return re.sub(r", 256>$", ">", name[i:name.index(">", i) + 1])
     for k in ("lk_kernel_st", "lk_kernel_lg", "lk_kernel", "pyramid_kernel", "read_u8", "read_x4", "write_u8",
               "write_x4"):
         if k in name:
