@@ -403,13 +403,19 @@ __device__ __forceinline__ float add16m(float acc, const bxf4 &a, const bxf4 &b,
 #ifndef PSN_BX_FLAGS
 #define PSN_BX_FLAGS 1
 #endif
+// fallback tile geometry of the no-tail builds from the tile's unit range alone
+// (no division by the row's quads; 0: the general formula of the tail builds)
+#ifndef PSN_BX_GEO_NT
+#define PSN_BX_GEO_NT 1
+#endif
 __device__ __forceinline__ void bx_prio_hi() { __builtin_amdgcn_s_setprio(PSN_BX_PRIO); }
 __device__ __forceinline__ void bx_prio_lo() { __builtin_amdgcn_s_setprio(0); }
 // UNIFORM (no-tail builds): every chain lane has nbmax blocks, so no block is
 // masked and the adds carry no select on the dependent chain; an odd last
 // block is summed after the loop.
 template <bool UNIFORM>
-__device__ __forceinline__ float chain_sum_pl(const float *p, int len, int nbmax, float acc) {
+__device__ __forceinline__ float chain_sum_pl(const float *p, int len, int nbmax, float acc
+                                              PSN_STAMPS_ONLY(, unsigned *first_wait = nullptr)) {
     unsigned ad = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float *)p;
     const int nb = (len + 15) >> 4;
     if (nbmax <= 0) return acc;
@@ -418,7 +424,18 @@ __device__ __forceinline__ float chain_sum_pl(const float *p, int len, int nbmax
     // workgroups' waves: issue it first
     __builtin_amdgcn_s_setprio(3);
     bxf4 a0, a1, a2, a3, c0, c1, c2, c3;
+#ifdef PSN_LK_STAMPS
+    // the first block's LDS round trip, with nothing summed in front of it (and
+    // one clock read: PSN_CLK waits for its own value)
+    unsigned long long t0_, t1_;
+    PSN_CLK(t0_);
+#endif
     BX_LD(a0, a1, a2, a3, ad, 0, 16, 32, 48);
+#ifdef PSN_LK_STAMPS
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : : "memory");
+    PSN_CLK(t1_);
+    if (first_wait && threadIdx.x == 0) *first_wait += (unsigned)(t1_ - t0_);  // (an LDS counter of thread 0)
+#endif
     if constexpr (UNIFORM) {
         int b = 0;
         for (; b + 1 < nbmax; b += 2) {

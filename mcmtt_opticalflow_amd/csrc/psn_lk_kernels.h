@@ -302,6 +302,28 @@ __host__ __device__ inline int bx_region(int n) { return ((n + 15) & ~15) + 4; }
 // waves in the two-wave build): one plane (4 SSE2 lane regions + the tail region)
 // holds at most 4*tile*UPT terms + padding.
 __host__ __device__ inline int bx_pc(int upt, int tile = kBxTile) { return 4 * tile * upt + 96; }
+// Chain slots of a fallback tile, the units [ua, ub) of the window (row-major, qw
+// per row): the first nq quads of a row feed the four SSE2 lane chains (one slot
+// per quad), its pixels from n4 on (tl of them) the tail chain. sa / ta: the
+// slots before the tile, nsse / ntail: the tile's own.
+__host__ __device__ inline void bx_tile_slots(int ua, int ub, int qw, int nq, int n4, int tl, int &sa, int &ta,
+                                              int &nsse, int &ntail) {
+    const int ya = ua / qw, qa = ua % qw, yb = ub / qw, qb = ub % qw;
+    const int pa = 4 * qa - n4 > 0 ? 4 * qa - n4 : 0, pb = 4 * qb - n4 > 0 ? 4 * qb - n4 : 0;
+    sa = ya * nq + (qa < nq ? qa : nq);
+    ta = ya * tl + (pa < tl ? pa : tl);
+    nsse = yb * nq + (qb < nq ? qb : nq) - sa;
+    ntail = yb * tl + (pb < tl ? pb : tl) - ta;
+}
+// The same where every quad is an SSE2 quad (nq == qw, tl == 0: the no-tail
+// builds): a unit's slot is its index, so the tile's slots are its unit range --
+// no division by the row's quads on the tile loops' path. A full tile of such a
+// build is whole 16-float blocks (tile * upt % 16 == 0 for every instantiated
+// build: 32 threads x an even upt, 16 x 8), so only a window's last tile has a
+// pad to zero.
+__host__ __device__ inline void bx_tile_slots_nt(int ua, int ub, int &sa, int &ta, int &nsse, int &ntail) {
+    sa = ua, ta = 0, nsse = ub - ua, ntail = 0;
+}
 struct BxLayout {
     int jr, un, pb, total;
     __host__ __device__ BxLayout(int w, int h, int upt, int hw = 1, int tile = kBxTile) {

@@ -1886,7 +1886,11 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
 // ---------------------------------------------------------------------------
 // Diagnostic phase clocks (PSN_LK_STAMPS, psn_lk_stamps.h; thread 0's view):
 // accumulated s_memtime ticks per phase in bx_acc, written as stamps[wg][0..15]
-// at the end.
+// at the end. stamps[wg][19..30]: per fallback tile, the chain lane's time split
+// (tools/bx_stamps.py) -- A fallback 19 its wave's next-tile write, 20 geometry +
+// pad, 21 chain sums, 22 barrier wait, 23 tiles, 24 first-block wait (inside 21);
+// b fallback, flag loop 25 flag wait, 26 geometry + pad, 27 chain sums, 28 tiles;
+// barrier loop 29 chain sums (inside 12); 30 first-block wait of either loop.
 // NT: the workgroup size. kBxNT2 is the two-wave build (QT below): the same
 // kernel with two waves' records, err partials and staging strides, and fallback
 // tiles of a quarter wave (kBxTile2 threads), each written by its whole wave.
@@ -1975,6 +1979,14 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
     int par = 0;
 #ifdef PSN_LK_STAMPS
     unsigned long long bx_acc[16] = {}, bx_t = 0, bx_t0 = 0, bx_r0 = 0;
+    // the fallback tile splits (stamps 19-30) add up in the 16 free words of the
+    // scratch region, by thread 0 alone: as registers they spill in every build
+    unsigned *bx_tl = (unsigned *)(RS + 32);
+    if (threadIdx.x < 12) bx_tl[threadIdx.x] = 0;  // ordered by the first level barrier
+#define BX_TL(slot, d)                                      \
+    do {                                                    \
+        if (threadIdx.x == 0) bx_tl[(slot)-19] += (unsigned)(d); \
+    } while (0)
     PSN_CLK_ORDERED(bx_t0);
     bx_t = bx_t0;
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(bx_r0) : : "memory");  // 100 MHz
@@ -2165,12 +2177,23 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
                 const int cl = chl ? ftid : 0, cs = cl / 5, cc = cl - 5 * cs;
                 float acc = (float)base0;  // |base0| <= 2^24: exact
                 const int g_last = (U - 1) / (TG * UPT), g_first = h0 * TPH;
-                auto geoA = [&](int g, int &sa, int &ta, int &nsse, int &ntail) {
+                // The tile's chain slots (bx_tile_slots). No-tail builds take the short form
+                // (PSN_BX_GEO_NT: no division on the tile loop's path) everywhere but in the
+                // half-wave writers, writeA_nt and the b fallback's write_tile_nt (shortT
+                // false): those hold the register peak of the <4 / 8 / 10, true> builds,
+                // which moves with the form (121 / 151 / 164 for 122 / 152 / 167, the
+                // figures tests/test_bx_two_wave_plan.py holds them to).
+                auto geoA_g = [&](int g, int &sa, int &ta, int &nsse, int &ntail, auto shortT) {
                     const int ua = TG * UPT * g, ub = min(ua + TG * UPT * HW, U);
-                    sa = (ua / QW) * nqA + min(ua % QW, nqA);
-                    ta = (ua / QW) * tA + min(max(4 * (ua % QW) - nA4, 0), tA);
-                    nsse = (ub / QW) * nqA + min(ub % QW, nqA) - sa;
-                    ntail = (ub / QW) * tA + min(max(4 * (ub % QW) - nA4, 0), tA) - ta;
+                    if constexpr (NOTAIL && PSN_BX_GEO_NT && decltype(shortT)::value) {
+                        static_assert((TG * UPT) % 16 == 0, "a full no-tail tile has no pad");
+                        bx_tile_slots_nt(ua, ub, sa, ta, nsse, ntail);
+                    } else {
+                        bx_tile_slots(ua, ub, QW, nqA, nA4, tA, sa, ta, nsse, ntail);
+                    }
+                };
+                auto geoA = [&](int g, int &sa, int &ta, int &nsse, int &ntail) {
+                    geoA_g(g, sa, ta, nsse, ntail, std::true_type());
                 };
                 auto unitA = [&](int yk, int qk, bool uv, unsigned x0, unsigned x1, unsigned y0_, unsigned y1_, float *buf,
                                  int S, int P, int sa, int ta) {
@@ -2205,7 +2228,7 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
                     constexpr bool lower = decltype(lowerT)::value;
                     if ((ftid >> 6) != (g >> 1)) return;
                     int sa, ta, nsse, ntail;
-                    geoA(g, sa, ta, nsse, ntail);
+                    geoA_g(g, sa, ta, nsse, ntail, std::false_type());  // (the general form: see geoA_g)
                     const int S = bx_region(nsse), P = 4 * S + bx_region(ntail);
                     const bool up = (ftid & 32) != 0;
                     const int ub = lower ? (up ? (ftid ^ 32) * UPT + K1 : ftid * UPT) : (up ? ftid * UPT + K1 : (ftid ^ 32) * UPT);
@@ -2355,12 +2378,20 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
                 __syncthreads();
                 for (int g = g_first, t = 0; g <= g_last; g += HW, t ^= 1) {
                     float *cur = PL + t * PCA, *nxt = PL + (t ^ 1) * PCA;
+#ifdef PSN_LK_STAMPS
+                    unsigned long long tc0, tc1, tc2, tc3, tc4, tc5;
+                    PSN_CLK_ORDERED(tc0);
+#endif
                     if (g + HW <= g_last) {
                         if constexpr (QT)
                             writeA_qt(g + HW, nxt, 0);
                         else
                             writeA(g + HW, nxt);
                     }
+#ifdef PSN_LK_STAMPS
+                    PSN_CLK_ORDERED(tc1);
+                    tc2 = tc3 = tc1;
+#endif
                     if ((ftid >> 6) == 0) {
                         int sa, ta, nsse, ntail;
                         geoA(g, sa, ta, nsse, ntail);
@@ -2368,11 +2399,25 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
                         const int len = chl ? (cc < 4 ? nsse : ntail) : 0;
                         // (no-tail: every chain lane's length is nsse)
                         const int nbmax = NOTAIL ? (nsse + 15) >> 4 : __builtin_amdgcn_readlane(wave_max_scan((len + 15) >> 4), 63);
+                        PSN_CLK_ORDERED(tc2);
                         // (no-tail: the tail-chain lanes keep acc = 0)
-                        if (chl && (!NOTAIL || cc < 4)) acc = chain_sum_pl<NOTAIL>(cur + cs * P + cc * S, len, nbmax, acc);
+                        if (chl && (!NOTAIL || cc < 4))
+                            acc = chain_sum_pl<NOTAIL>(cur + cs * P + cc * S, len, nbmax, acc PSN_STAMPS_ONLY(, &bx_tl[24 - 19]));
+                        PSN_CLK_ORDERED(tc3);
                         if (g + HW <= g_last) padA(g + HW, nxt);
                     }
+#ifdef PSN_LK_STAMPS
+                    PSN_CLK_ORDERED(tc4);
+#endif
                     __syncthreads();
+#ifdef PSN_LK_STAMPS
+                    PSN_CLK_ORDERED(tc5);  // (chain lane 0's view, as the b fallback's stamps below)
+                    BX_TL(19, tc1 - tc0);                  // its wave's write of the next tile
+                    BX_TL(20, (tc2 - tc1) + (tc4 - tc3));  // geometry + pad
+                    BX_TL(21, tc3 - tc2);                  // chain sums (first-block wait: 24)
+                    BX_TL(22, tc5 - tc4);                  // barrier wait
+                    BX_TL(23, 1);
+#endif
                 }
                 if (ftid < 64) {  // wave 0 combines in the SSE2 build's order
 #pragma unroll
@@ -2573,12 +2618,18 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
                 const int cl = chl ? ftid : 0, cs = cl / 5, cc = cl - 5 * cs;
                 float acc = (float)base0;
                 const int g_last = (U - 1) / (TG * UPT), g_first = h0 * TPH;
-                auto tile_geo = [&](int g, int &sa, int &ta, int &nsse, int &ntail) {
+                // (as the A fallback's geoA_g)
+                auto tile_geo_g = [&](int g, int &sa, int &ta, int &nsse, int &ntail, auto shortT) {
                     const int ua = TG * UPT * g, ub = min(ua + TG * UPT * HW, U);
-                    sa = (ua / QW) * nqB + min(ua % QW, nqB);
-                    ta = (ua / QW) * tB + min(max(4 * (ua % QW) - n8, 0), tB);
-                    nsse = (ub / QW) * nqB + min(ub % QW, nqB) - sa;
-                    ntail = (ub / QW) * tB + min(max(4 * (ub % QW) - n8, 0), tB) - ta;
+                    if constexpr (NOTAIL && PSN_BX_GEO_NT && decltype(shortT)::value) {
+                        static_assert((TG * UPT) % 16 == 0, "a full no-tail tile has no pad");
+                        bx_tile_slots_nt(ua, ub, sa, ta, nsse, ntail);
+                    } else {
+                        bx_tile_slots(ua, ub, QW, nqB, n8, tB, sa, ta, nsse, ntail);
+                    }
+                };
+                auto tile_geo = [&](int g, int &sa, int &ta, int &nsse, int &ntail) {
+                    tile_geo_g(g, sa, ta, nsse, ntail, std::true_type());
                 };
                 // one unit's b products into the tile's chain regions
                 auto tile_unit = [&](int yk, int qk, bool uv, const unsigned (&ip)[2], const unsigned (&xp)[2],
@@ -2735,7 +2786,7 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
                     constexpr bool lower = decltype(lowerT)::value;
                     const int zf = opaque256();
                     int sa, ta, nsse, ntail;
-                    tile_geo(g, sa, ta, nsse, ntail);
+                    tile_geo_g(g, sa, ta, nsse, ntail, std::false_type());  // (the general form: see geoA_g)
                     const int S = bx_region(nsse), P = 4 * S + bx_region(ntail);
                     const bool up = (ftid & 32) != 0;
                     // lower tile: lane l < 32 its unit k, lane l + 32 lane l's unit K1 + k;
@@ -2814,7 +2865,12 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
                     if (wv == 0) {
                         for (int g = h0; g <= g_last; g++) {
                             const int b = (g - h0) % 3;
+#ifdef PSN_LK_STAMPS
+                            unsigned long long tf0, tf1, tf2, tf3, tf4;
+                            PSN_CLK_ORDERED(tf0);
+#endif
                             spin(b, tag(g));
+                            PSN_CLK_ORDERED(tf1);
                             float *cur = PL + b * 2 * PC;
                             int sa, ta, nsse, ntail;
                             tile_geo(g, sa, ta, nsse, ntail);
@@ -2825,9 +2881,19 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
                                 for (int i = len; i < ((len + 15) & ~15); i++) rg[i] = 0.f;
                             }
                             const int nbmax = NOTAIL ? (nsse + 15) >> 4 : __builtin_amdgcn_readlane(wave_max_scan((len + 15) >> 4), 63);
-                            if (chl && (!NOTAIL || cc < 4)) acc = chain_sum_pl<NOTAIL>(cur + cs * P + cc * S, len, nbmax, acc);
+                            PSN_CLK_ORDERED(tf2);
+                            if (chl && (!NOTAIL || cc < 4))
+                                acc = chain_sum_pl<NOTAIL>(cur + cs * P + cc * S, len, nbmax, acc PSN_STAMPS_ONLY(, &bx_tl[30 - 19]));
+                            PSN_CLK_ORDERED(tf3);
                             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                             if (fl == 0) FLG[3 + b] = tag(g);
+#ifdef PSN_LK_STAMPS
+                            PSN_CLK_ORDERED(tf4);
+                            BX_TL(25, tf1 - tf0);                  // wait for the tile's ready flag
+                            BX_TL(26, (tf2 - tf1) + (tf4 - tf3));  // geometry + pad + the consumed flag
+                            BX_TL(27, tf3 - tf2);                  // chain sums (first-block wait: 30)
+                            BX_TL(28, 1);
+#endif
                         }
                     }
                 } else
@@ -2849,8 +2915,9 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
                             write_tile(g + HW, nxt);
                     }
 #ifdef PSN_LK_STAMPS
-                    unsigned long long tc0, tc1, tc2;
+                    unsigned long long tc0, tc1, tc2, tc3, tc4;
                     PSN_CLK_ORDERED(tc0);
+                    tc3 = tc4 = tc0;
 #endif
                     if ((ftid >> 6) == 0) {
                         int sa, ta, nsse, ntail;
@@ -2859,8 +2926,11 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
                         const int len = chl ? (cc < 4 ? nsse : ntail) : 0;
                         // (no-tail: every chain lane's length is nsse)
                         const int nbmax = NOTAIL ? (nsse + 15) >> 4 : __builtin_amdgcn_readlane(wave_max_scan((len + 15) >> 4), 63);
+                        PSN_CLK_ORDERED(tc3);
                         // (no-tail: the tail-chain lanes keep acc = 0)
-                        if (chl && (!NOTAIL || cc < 4)) acc = chain_sum_pl<NOTAIL>(cur + cs * P + cc * S, len, nbmax, acc);
+                        if (chl && (!NOTAIL || cc < 4))
+                            acc = chain_sum_pl<NOTAIL>(cur + cs * P + cc * S, len, nbmax, acc PSN_STAMPS_ONLY(, &bx_tl[30 - 19]));
+                        PSN_CLK_ORDERED(tc4);
                         if (g + HW <= g_last) pad_tile(g + HW, nxt);
                     }
 #ifdef PSN_LK_STAMPS
@@ -2869,7 +2939,8 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
                     __syncthreads();
 #ifdef PSN_LK_STAMPS
                     PSN_CLK_ORDERED(tc2);
-                    bx_acc[12] += tc1 - tc0;  // (chain lane 0's view) chain sums incl. its own tile writes
+                    bx_acc[12] += tc1 - tc0;  // (chain lane 0's view) geometry + chain sums + pad
+                    BX_TL(29, tc4 - tc3);     // of it: the chain sums alone (first-block wait: 30)
                     bx_acc[13] += tc2 - tc1;  // barrier wait
                     bx_acc[14]++;
 #endif
@@ -2988,6 +3059,7 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         if (tid == 0 && A.stamps) {  // thread 0: also the chain lane of the tile stamps 12-14
             for (int i = 0; i < 16; i++) A.stamps[(size_t)g * 64 + i] = bx_acc[i];
+            for (int i = 19; i < 31; i++) A.stamps[(size_t)g * 64 + i] = bx_tl[i - 19];  // fallback tile splits
             // residency: realtime (100 MHz) start / end and the CU it ran on
             A.stamps[(size_t)g * 64 + 16] = bx_r0;
             A.stamps[(size_t)g * 64 + 17] = r1;

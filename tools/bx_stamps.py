@@ -4,7 +4,9 @@ build (make -C mcmtt_opticalflow_amd/csrc stamps; run with
 the stamps build, mcmtt_opticalflow_amd/lib/libpsn_lk_stamps.so). Tracker2D-like windows on the synthetic
 1080p scene, the reference's default criteria (30, 0.01), maxLevel 3.
 Prints per-workgroup mean / slowest cycles per phase (s_memtime ticks, thread
-0's view) and the serial-chain fraction of the iterations.
+0's view), the serial-chain fraction of the iterations and, per fallback tile,
+the chain lane's time split four ways for the A and the b fallback.
+STAMPS_LIB=path runs another stamps build (make ... EXTRA=-DPSN_BX_GEO_NT=0).
 
   WIN=64 WINH=160 NPTS=630 python tools/bx_stamps.py
   WIN=64 WINH=64 NPTS=2048 VARIANTS=bx_waves=4 python tools/bx_stamps.py   # the four-wave build; bx_waves=2:
@@ -12,6 +14,7 @@ Prints per-workgroup mean / slowest cycles per phase (s_memtime ticks, thread
 """
 import json
 import os
+import re
 import sys
 
 import numpy as np
@@ -33,7 +36,7 @@ def main():
     sc = synth.make_scene(0, 1920, 1080, npts, nboxes=8)
     f0, f1 = sc.frame(0), sc.frame(1)
     pts = sc.points_at(1)
-    L = _lib.load(_lib.STAMPS_LIB_PATH)
+    L = _lib.load(os.environ.get("STAMPS_LIB", _lib.STAMPS_LIB_PATH))  # STAMPS_LIB: another stamps build (A/B)
     st = hiprt.DeviceBuffer(npts * 64 * 8)
     variants = {k: int(v) for k, v in (kv.split("=") for kv in os.environ.get("VARIANTS", "").split(",") if kv)}
     with lk.LKContext(1920, 1080, ring_slots=2, max_level_cap=3, variants=variants) as ctx:
@@ -63,6 +66,34 @@ def main():
     out["serial_b_tiles_per_serial_iteration"] = round(float(s[:, 14].sum() / max(s[:, 11].sum(), 1)), 2)
     out["serial_b_per_tile_chain_lane_view"] = {"chain_sum": round(float(s[:, 12].sum() / nt), 1),
                                                 "barrier_wait": round(float(s[:, 13].sum() / nt), 1)}
+    # Per fallback tile, the chain lane's time four ways (stamps 19-30, chain lane
+    # 0's view): geometry + pad, the first block's LDS round trip (nothing summed
+    # in front of it), the additions behind it, and the wait for the next tile (a
+    # workgroup barrier, or the tile's ready flag in the flag hand-off loop). The
+    # cycles per term are over a full tile's terms per chain (tile threads x units
+    # per thread, one half-wave granule per tile).
+    m = re.search(r"lk_kernel_bx<(\d+), true(?:, (\d+))?>", out["kernel"])
+    terms = int(m.group(1)) * (16 if m.group(2) == "128" else 32) if m else None
+
+    def split(n, geo, first, chain, wait, extra=None):
+        n = max(float(n), 1.0)
+        d = {"tiles_per_workgroup": round(n / npts, 2), "geometry_pad": round(float(geo) / n, 1),
+             "first_block_wait": round(float(first) / n, 1), "additions": round(float(chain - first) / n, 1),
+             "barrier_or_flag_wait": round(float(wait) / n, 1)}
+        if terms:
+            d["terms_per_full_tile"] = terms
+            d["cycles_per_term_additions"] = round(float(chain - first) / n / terms, 2)
+            d["cycles_per_term_all_but_wait"] = round(float(geo + chain) / n / terms, 2)
+        if extra:
+            d.update({k: round(float(v) / n, 1) for k, v in extra.items()})
+        return d
+
+    c = s[:, 19:31].sum(0)  # stamps 19 .. 30
+    out["a_fallback_per_tile"] = split(c[4], c[1], c[5], c[2], c[3], {"own_wave_next_tile_write": c[0]})
+    if s[:, 28].sum() > 0:  # the flag hand-off loop (four-wave builds, half-wave tiles)
+        out["b_fallback_per_tile"] = split(c[9], c[7], c[11], c[8], c[6]) | {"loop": "flags"}
+    else:
+        out["b_fallback_per_tile"] = split(s[:, 14].sum(), s[:, 12].sum() - c[10], c[11], c[10], s[:, 13].sum()) | {"loop": "barrier"}
     it = max(s[:, 10].sum(), 1)
     out["per_iteration"] = {k: round(float(ph[:, i].sum() / it), 1) for i, k in enumerate(PHASES) if i >= 3}
     out["per_iteration"]["b_publish_only"] = round(float(s[:, 9].sum() / it), 1)  # inside b_publish_eval
