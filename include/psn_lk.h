@@ -6,8 +6,10 @@
  *   cv::calcOpticalFlowPyrLK(curr, prev, ...)  backward, PSNWhere_Tracker2D.cpp:776-782
  *   cv::calcOpticalFlowPyrLK(prev, curr, ...)  forward,  PSNWhere_Tracker2D.cpp:871-877
  * and the per-frame gray ring buffer they read
- *   cvtColor(BGR2GRAY) + resize(scale 1.0) into m_vecPtGrayFrameBuffer,
- *   PSNWhere_Tracker2D.cpp:256-263 (ingest), :310-316 (rotation), .h:187.
+ *   cvtColor(BGR2GRAY) + resize(PSN_2D_OPTICALFLOW_SCALE) into
+ *   m_vecPtGrayFrameBuffer, PSNWhere_Tracker2D.cpp:256-263 (ingest), :310-316
+ *   (rotation), .h:187. psn_lk_create is scale 1.0; psn_lk_create_scaled takes
+ *   the scale (the resize runs on the device at every push).
  *
  * Plain C: pointers and sizes only, no C++/torch types. Every entry point
  * returns 0 (PSN_LK_OK) or a negative PSN_LK_ERR_*; no exception or abort
@@ -112,6 +114,46 @@ int psn_lk_create(int device, int width, int height, int ring_slots, int max_lev
 void psn_lk_destroy(psn_lk_ctx *ctx);
 const char *psn_lk_last_error(psn_lk_ctx *ctx);
 
+/* ---- a reduced optical-flow scale (PSN_2D_OPTICALFLOW_SCALE, PSNWhere_Tracker2D.cpp:17-18) ----
+ * The reference converts a frame to gray and resizes it into the ring
+ *   cv::resize(gray, ring[slot], cv::Size(width * SCALE, height * SCALE))   :260-262
+ * and runs GridFAST and both LK calls on the reduced frame. A scaled context
+ * does the same: scale is a double in (0, 1], fixed per context, and the LK size
+ * is lw = (int)((double)width * scale), lh = (int)((double)height * scale).
+ * width x height is the SOURCE size: every psn_lk_push_frame* variant takes
+ * source-size frames (a JPEG must have the source size), and the colour source
+ * of a slot stays the full-size frame: psn_lk_box_histograms clips rects to the
+ * source size and counts there. The ring, psn_lk_level_size, psn_lk_read_level,
+ * LK queries and GridFAST rois all use the LK size. psn_calc_optical_flow_pyr_lk
+ * keeps taking gray images of the LK size: it is calcOpticalFlowPyrLK itself,
+ * which the reference calls on frames already resized.
+ * Each push runs one more kernel (BGR2GRAY with RGB2Gray<uchar>, then the
+ * resize, into a per-slot gray plane that the pyramid build reads as a 1-channel
+ * source); in FUSED mode it runs at push time and only the pyramid build is
+ * deferred. A context whose LK size equals the source size (scale 1.0) launches
+ * nothing extra and is psn_lk_create's context. Results are identical in every
+ * overlap mode. psn_lk_enable_timing's push figure includes the resize launch.
+ * The arithmetic is OpenCV 2.4.6 resize(INTER_LINEAR) for CV_8UC1 [OCV246
+ * imgproc/src/imgwarp.cpp], restated (no test here pins it against the library):
+ *   scale_x = 1.0 / ((double)lw / width), per output column dx
+ *   fx = (float)((dx + 0.5) * scale_x - 0.5); sx = floor(fx); fx -= sx  (float)
+ *   sx < 0: sx = 0, fx = 0;  sx >= width - 1: sx = width - 1, fx = 0
+ *   a0 = cvRound((1.f - fx) * 2048), a1 = cvRound(fx * 2048)   (shorts)
+ *   D = S[sx] * a0 + S[min(sx + 1, width - 1)] * a1
+ * rows the same with fy NOT zeroed at the borders and the source rows
+ * clamp(sy, 0, height - 1), clamp(sy + 1, 0, height - 1);
+ *   out = (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2.
+ * PSN_LK_ERR_ARG for a scale that is NaN, <= 0 or > 1, or an LK size below 1 px. */
+int psn_lk_scaled_size(int width, int height, double scale, int *lw, int *lh); /* host only */
+/* The tables of one axis (host only): ofs[dst] = sx (border rule applied when
+ * is_x, else the unclamped sy), coef[dst][2] = {a0, a1}. */
+int psn_lk_resize_plan(int src, int dst, int *ofs, int16_t *coef, int is_x);
+int psn_lk_create_scaled(int device, int width, int height, double scale, int ring_slots, int max_level_cap,
+                         psn_lk_ctx **out);
+/* The size of pushed frames and the scale (width x height and 1.0 for a psn_lk_create context). */
+int psn_lk_source_size(psn_lk_ctx *ctx, int *w, int *h);
+int psn_lk_scale(psn_lk_ctx *ctx, double *s);
+
 /* Use an external HIP stream (hipStream_t as void*); NULL restores the
  * context's own stream. */
 int psn_lk_set_stream(psn_lk_ctx *ctx, void *hip_stream);
@@ -120,7 +162,8 @@ int psn_lk_sync(psn_lk_ctx *ctx);
 
 /* Ingest one frame into ring slot `slot` and build its pyramid on device
  * (replaces cvtColor(BGR2GRAY) + resize + the per-call pyramid rebuilds,
- * PSNWhere_Tracker2D.cpp:257-262). channels: 1 (gray) or 3 (BGR).
+ * PSNWhere_Tracker2D.cpp:257-262). channels: 1 (gray) or 3 (BGR). The frame
+ * has the context's source size (psn_lk_source_size).
  * _device: `dev` is a device pointer; the call is asynchronous on the
  * context stream. Host variant copies and returns after enqueueing. */
 int psn_lk_push_frame(psn_lk_ctx *ctx, int slot, const uint8_t *host, int stride, int channels);
@@ -137,7 +180,7 @@ int psn_lk_push_frame_device(psn_lk_ctx *ctx, int slot, const uint8_t *dev, int 
 int psn_lk_push_frame_async(psn_lk_ctx *ctx, int slot, const uint8_t *host, int stride, int channels);
 
 /* The same from a compressed frame: a baseline JPEG (include/psn_jpeg.h) of
- * the context's size is decoded on the device (cv::imread, main.cpp:144) into
+ * the context's source size is decoded on the device (cv::imread, main.cpp:144) into
  * the slot's staging buffer and its pyramid built from the BGR result, all on
  * the ingest stream; `jpeg` is copied before the call returns. */
 int psn_lk_push_frame_jpeg(psn_lk_ctx *ctx, int slot, const uint8_t *jpeg, size_t len);
@@ -186,7 +229,8 @@ int psn_lk_track_device_counted_strided(psn_lk_ctx *ctx, const psn_lk_query *q, 
 
 /* One-shot cv::calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, status,
  * err, winSize, maxLevel, criteria, flags, minEigThreshold) on two host gray
- * images of the context's size, using two scratch slots of the context. */
+ * images of the context's LK size (psn_lk_level_size(ctx, 0): a scaled context
+ * does not resize them), using two scratch slots of the context. */
 int psn_calc_optical_flow_pyr_lk(psn_lk_ctx *ctx, const uint8_t *prev_img, const uint8_t *next_img,
                                  int stride, const float *prev_pts, float *next_pts, uint8_t *status,
                                  float *err, int npts, const psn_lk_params *params);
@@ -196,8 +240,10 @@ int psn_lk_read_level(psn_lk_ctx *ctx, int slot, int level, uint8_t *host, int s
 int psn_lk_level_size(psn_lk_ctx *ctx, int level, int *w, int *h);
 
 /* Device-side kernel timing with HIP events recorded on the context stream
- * around every `every`-th psn_lk_push_frame* build launch (pyramid kernel)
- * and psn_lk_track* call (LK launch, including a fused build). `capacity` =
+ * around every `every`-th psn_lk_push_frame* build launch (pyramid kernel, and
+ * before it the resize launch of a scaled context; a FUSED-mode device push of a
+ * scaled context times its resize launch alone, the deferred build runs inside
+ * an LK launch) and psn_lk_track* call (LK launch, including a fused build). `capacity` =
  * timed calls of each kind kept in an event ring (0 disables); every >= 1
  * (each event pair costs a few microseconds of GPU time, so sampling keeps
  * the measurement from slowing the measured loop). psn_lk_timing_stats waits
@@ -345,7 +391,7 @@ int psn_rgbhist_device(const psn_rgbhist_rect *d_rects, int nrect, uint32_t *d_c
  * psn_gridfast_detect_device_sets: set i = nrects[i] rects {x, y, w, h} on the
  * colour frame last pushed into ring slot slots[i], the sets' rects consecutive
  * in `rects` and their counters in `counts` (host, [sum nrects][48]). The rects
- * are clipped to the frame here (x < 0 -> 0, y < 0 -> 0, x + w > width ->
+ * are clipped to the frame (its source size) here (x < 0 -> 0, y < 0 -> 0, x + w > width ->
  * w = width - x, y + h > height -> h = height - y); an empty rect gives zeros.
  * One launch for all sets; synchronous, on a stream of the context's own that
  * waits for each slot's upload / decode / build but not for queued LK work.

@@ -38,7 +38,10 @@ extern "C" {
  *   nsteps   [ndet]          out: last step that kept >= 4 inliers
  *   last_step[ndet]          in, nullable: the chain's last step (the ring of the
  *                            detection's camera holds frames back to t - last_step);
- *                            at that step the count is cleared after the results */
+ *                            at that step the count is cleared after the results
+ *   scale                    PSN_2D_OPTICALFLOW_SCALE (> 0; 1.0 = full size): boxes and points are
+ *                            in the scaled frame; LocalSearchKLT's minimum movement is 0.1 * scale
+ *                            and its neighbour window box.w * 0.2 * scale (:481, :502), in double */
 typedef struct psn_t2d_chain_dev {
     int ndet, cap;
     const double *boxes;
@@ -50,6 +53,7 @@ typedef struct psn_t2d_chain_dev {
     int *set_cnt;
     int *nsteps;
     const int *last_step;
+    double scale;
 } psn_t2d_chain_dev;
 
 /* LocalSearchKLT + inlier compaction of chain step `step` (1..3) for every

@@ -67,10 +67,39 @@ double psn_t2d_box_matching_cost(psn_rect a, psn_rect b);
  * indices of the inlier points (capacity n), *n_inliers their count. */
 int psn_t2d_local_search_klt(psn_rect pre_box, const float *pre_xy, const float *cur_xy, int n, psn_rect *out_box,
                              int *inlier_idx, int *n_inliers);
+/* The same at PSN_2D_OPTICALFLOW_SCALE = scale (the function above is scale 1.0):
+ * pre_box and the points are in the scaled frame; a vector moves unless its norm
+ * is below 0.1 * scale (:481) and the neighbour window is pre_box.w * 0.2 * scale
+ * (:502; pre_box is scaled already, the reference applies the scale twice).
+ * PSN_LK_ERR_ARG for a scale that is NaN, <= 0 or > 1. */
+int psn_t2d_local_search_klt_scaled(psn_rect pre_box, const float *pre_xy, const float *cur_xy, int n, double scale,
+                                    psn_rect *out_box, int *inlier_idx, int *n_inliers);
+
+/* ---- a reduced optical-flow scale (PSN_2D_OPTICALFLOW_SCALE, :17-18) ----
+ * psn_t2d_create_scaled / psn_t2d_group_create_scaled run the whole 2D flow path
+ * in the frame resized to lw x lh = (int)(width * scale) x (int)(height * scale)
+ * (psn_lk_create_scaled, include/psn_lk.h; scale a double in (0, 1], fixed per
+ * object; psn_t2d_create / psn_t2d_group_create are scale 1.0). width x height
+ * stays the size of pushed frames. The scale enters where the reference's does:
+ *   GridFAST roi      box.scale(s).cropWithSize(lw, lh).cv()            (:735)
+ *   backward window   (int)(box.scale(s).w), squared                     (:770)
+ *   forward window    (int)(w * s) x (int)(h * s) of the tracker's last box (:870)
+ *   LocalSearchKLT    on the scaled box, psn_t2d_local_search_klt_scaled (:481, :502)
+ *   recovered boxes   .scale(1.0 / s), 1 / s formed once as a double     (:789, :894)
+ * Feature points -- detection features and sets, tracker features / tracked,
+ * the result's featurePointsPrev / Curr -- stay in the coordinates of the
+ * resized frame, as the reference leaves them; the forward in-box gate compares
+ * them with the unscaled detection box (:914-918). Detection boxes, result
+ * boxes, heads, matching costs, validation and appearance rects are in source
+ * coordinates; psn_t2d_group_appearance counts on the full-size colour frame.
+ * The window limits (winSize > 2, psn_lk_window_supported) apply to the scaled
+ * windows. PSN_LK_ERR_ARG for a scale that is NaN, <= 0 or > 1, or a resized
+ * frame below 1 px. */
 
 /* One camera's flow stage: owns a psn_lk context with a ring of 4 pyramids. */
 typedef struct psn_t2d psn_t2d;
 int psn_t2d_create(int device, unsigned cam_id, int width, int height, psn_t2d **out);
+int psn_t2d_create_scaled(int device, unsigned cam_id, int width, int height, double scale, psn_t2d **out);
 void psn_t2d_destroy(psn_t2d *t);
 const char *psn_t2d_last_error(psn_t2d *t);
 /* Where the backward chain's LocalSearchKLT steps run: 1 (default) on the
@@ -78,7 +107,8 @@ const char *psn_t2d_last_error(psn_t2d *t);
  * back to back, one host sync per frame -- or 0 on the host between launches.
  * Results are identical. */
 int psn_t2d_set_device_chain(psn_t2d *t, int on);
-/* ingest frame t into the ring's newest slot (cvtColor + resize, :256-263) */
+/* ingest frame t (width x height, the size given at creation) into the ring's
+ * newest slot (cvtColor + resize by the scale, :256-263) */
 int psn_t2d_push_frame(psn_t2d *t, const uint8_t *frame, int stride, int channels);
 /* the same from a frame already in device memory (complete on the context's
  * stream order; psn_lk_push_frame_device semantics) */
@@ -151,7 +181,8 @@ typedef struct psn_track2d_result {
 /* Feature extraction of the backward chain (PSNWhere_Tracker2D.cpp:734-757) on
  * frame t (call after psn_t2d_push_frame): GridFAST (psn_gridfast_detect with
  * the "GridFAST" defaults) masked by each detection's rectROI =
- * box.cropWithSize(width, height).cv() (:736), shuffled by `seed` (the
+ * box.scale(s).cropWithSize(lw, lh).cv() (:736; s = 1, the frame size, unless
+ * the object was created _scaled), shuffled by `seed` (the
  * reference's unseeded std::random_shuffle, :752) and capped at
  * PSN_T2D_MAX_FEATURES. Fills dets[i].features / num_features; a detection
  * with fewer than PSN_T2D_MIN_FEATURES points is skipped by the backward step
@@ -250,6 +281,8 @@ typedef struct psn_t2d_group psn_t2d_group;
 #define PSN_T2D_FEATURES_GIVEN 0
 #define PSN_T2D_FEATURES_GRIDFAST 1
 int psn_t2d_group_create(int device, int ncams, const unsigned *cam_ids, int width, int height, psn_t2d_group **out);
+int psn_t2d_group_create_scaled(int device, int ncams, const unsigned *cam_ids, int width, int height, double scale,
+                                psn_t2d_group **out);
 void psn_t2d_group_destroy(psn_t2d_group *g);
 const char *psn_t2d_group_last_error(psn_t2d_group *g);
 void *psn_t2d_group_lk_context(psn_t2d_group *g);

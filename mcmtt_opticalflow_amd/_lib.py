@@ -176,6 +176,12 @@ def load(path: str | None = None):
     L.psn_lk_default_params.restype = None
     L.psn_lk_effective_max_level.argtypes = [ip] * 5
     L.psn_lk_create.argtypes = [ip, ip, ip, ip, ip, ctypes.POINTER(vp)]
+    if hasattr(L, "psn_lk_create_scaled"):  # (absent from the A/B experiments' older builds only)
+        L.psn_lk_scaled_size.argtypes = [ip, ip, ctypes.c_double, ctypes.POINTER(ip), ctypes.POINTER(ip)]
+        L.psn_lk_resize_plan.argtypes = [ip, ip, vp, vp, ip]
+        L.psn_lk_create_scaled.argtypes = [ip, ip, ip, ctypes.c_double, ip, ip, ctypes.POINTER(vp)]
+        L.psn_lk_source_size.argtypes = [vp, ctypes.POINTER(ip), ctypes.POINTER(ip)]
+        L.psn_lk_scale.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     L.psn_lk_destroy.argtypes = [vp]
     L.psn_lk_destroy.restype = None
     L.psn_lk_last_error.argtypes = [vp]

@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <mutex>
 #include <cstdarg>
 #include <cstdio>
@@ -25,13 +26,24 @@
 #include "psn_jpeg.h"
 #include "psn_gridfast.h"
 #include "psn_rgbhist.h"
+#include "psn_resize.h"
 #include "psn_lk_kernels.h"
 
 using psn::LevelDev;
 
 struct psn_lk_ctx {
     int device = 0;
-    int width = 0, height = 0;
+    int width = 0, height = 0;       // the LK size: ring, pyramids, LK queries, GridFAST rois
+    // psn_lk_create_scaled: pushed frames have the source size and are resized to
+    // the LK size (PSN_2D_OPTICALFLOW_SCALE); rz = the sizes differ, so every push
+    // runs resize_gray_kernel into the slot's gray plane and the pyramid build
+    // reads that plane as a 1-channel source
+    int src_w = 0, src_h = 0;
+    double scale = 1.0;
+    bool rz = false;
+    uint8_t *d_gray = nullptr;  // [nslots] planes of height rows, gray_pitch apart
+    int gray_pitch = 0;
+    int *d_rz_tab = nullptr;    // xofs[width] | xcoef[width] | yofs[height] | ycoef[height]
     int user_slots = 0, nslots = 0;  // user ring + 2 scratch slots (one-shot API)
     int nlevels = 0;                 // max_level_cap + 1
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -173,7 +185,8 @@ struct psn_lk_ctx {
 };
 
 static int set_err(psn_lk_ctx *c, int code, const char *fmt, ...);
-static int launch_build(psn_lk_ctx *c, const psn::PyrBuildArgs &a, hipStream_t s, int slot);
+static int launch_build(psn_lk_ctx *c, const psn::PyrBuildArgs &a, hipStream_t s, int slot,
+                        const psn::ResizeArgs *rz = nullptr);
 
 // Run a deferred (fused-mode) build now, as its own launch on the LK stream.
 static int flush_pending(psn_lk_ctx *c) {
@@ -349,7 +362,38 @@ int psn_lk_sdma_warmup_ms(int device, double *ms) {
     return PSN_LK_ERR_ARG;  // no context was created on this device yet
 }
 
-int psn_lk_create(int device, int width, int height, int ring_slots, int max_level_cap, psn_lk_ctx **out) {
+static int cv_round(float v) { return (int)lrint((double)v); }  // cvRound: to nearest, ties to even
+
+int psn_lk_scaled_size(int width, int height, double scale, int *lw, int *lh) {
+    if (width <= 0 || height <= 0 || !(scale > 0.0) || !(scale <= 1.0)) return PSN_LK_ERR_ARG;  // (NaN fails both)
+    const int w = (int)((double)width * scale), h = (int)((double)height * scale);
+    if (w < 1 || h < 1) return PSN_LK_ERR_ARG;
+    if (lw) *lw = w;
+    if (lh) *lh = h;
+    return PSN_LK_OK;
+}
+
+int psn_lk_resize_plan(int src, int dst, int *ofs, int16_t *coef, int is_x) {
+    if (src <= 0 || dst <= 0 || !ofs || !coef) return PSN_LK_ERR_ARG;
+    const double scale = 1.0 / ((double)dst / (double)src);
+    for (int d = 0; d < dst; d++) {
+        float f = (float)(((double)d + 0.5) * scale - 0.5);
+        int s = (int)floorf(f);
+        f -= (float)s;
+        if (is_x) {
+            if (s < 0) s = 0, f = 0.f;
+            if (s >= src - 1) s = src - 1, f = 0.f;
+        }
+        ofs[d] = s;
+        coef[2 * d] = (int16_t)cv_round((1.f - f) * 2048.f);
+        coef[2 * d + 1] = (int16_t)cv_round(f * 2048.f);
+    }
+    return PSN_LK_OK;
+}
+
+// The context of psn_lk_create (src = LK size) and psn_lk_create_scaled.
+static int create_impl(int device, int src_w, int src_h, double scale, int width, int height, int ring_slots,
+                       int max_level_cap, psn_lk_ctx **out) {
     if (!out || width <= 0 || height <= 0 || ring_slots <= 0 || max_level_cap < 0 ||
         max_level_cap > psn::kPyrMaxTop)
         return PSN_LK_ERR_ARG;
@@ -363,6 +407,10 @@ int psn_lk_create(int device, int width, int height, int ring_slots, int max_lev
     c->device = device;
     c->width = width;
     c->height = height;
+    c->src_w = src_w;
+    c->src_h = src_h;
+    c->scale = scale;
+    c->rz = src_w != width || src_h != height;
     c->user_slots = ring_slots;
     c->nslots = ring_slots + 2;
     c->nlevels = max_level_cap + 1;
@@ -443,7 +491,53 @@ int psn_lk_create(int device, int width, int height, int ring_slots, int max_lev
         if (hipEventCreateWithFlags(&c->slot_ready[i], kSlotEventFlags) != hipSuccess) return fail(PSN_LK_ERR_HIP);
         if (hipEventCreateWithFlags(&c->copy_done[i], kSlotEventFlags) != hipSuccess) return fail(PSN_LK_ERR_HIP);
     }
+    if (c->rz) {
+        // the resize tables, computed once, and one gray plane per slot on the ring's 256-B pitch
+        std::vector<int> ofs((size_t)std::max(width, height));
+        std::vector<int16_t> coef(2 * ofs.size());
+        std::vector<int> tab(2 * ((size_t)width + height));
+        for (int ax = 0; ax < 2; ax++) {
+            const int n = ax == 0 ? width : height;
+            int *t = tab.data() + (ax == 0 ? 0 : 2 * (size_t)width);
+            if (psn_lk_resize_plan(ax == 0 ? src_w : src_h, n, ofs.data(), coef.data(), ax == 0)) return fail(PSN_LK_ERR_ARG);
+            for (int i = 0; i < n; i++) {
+                t[i] = ofs[i];
+                t[n + i] = (int)((uint32_t)(uint16_t)coef[2 * i] | ((uint32_t)(uint16_t)coef[2 * i + 1] << 16));
+            }
+        }
+        if (hipMalloc(&c->d_rz_tab, tab.size() * sizeof(int)) != hipSuccess) return fail(PSN_LK_ERR_NOMEM);
+        if (hipMemcpy(c->d_rz_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(PSN_LK_ERR_HIP);
+        c->gray_pitch = (width + 255) & ~255;
+        const size_t bytes = (size_t)c->gray_pitch * height * c->nslots;
+        if (hipMalloc(&c->d_gray, bytes) != hipSuccess) return fail(PSN_LK_ERR_NOMEM);
+        if (hipMemset(c->d_gray, 0, bytes) != hipSuccess) return fail(PSN_LK_ERR_HIP);
+    }
     *out = c;
+    return PSN_LK_OK;
+}
+
+int psn_lk_create(int device, int width, int height, int ring_slots, int max_level_cap, psn_lk_ctx **out) {
+    return create_impl(device, width, height, 1.0, width, height, ring_slots, max_level_cap, out);
+}
+
+int psn_lk_create_scaled(int device, int width, int height, double scale, int ring_slots, int max_level_cap,
+                         psn_lk_ctx **out) {
+    int lw = 0, lh = 0;
+    if (psn_lk_scaled_size(width, height, scale, &lw, &lh)) return PSN_LK_ERR_ARG;
+    return create_impl(device, width, height, scale, lw, lh, ring_slots, max_level_cap, out);
+}
+
+int psn_lk_source_size(psn_lk_ctx *c, int *w, int *h) {
+    if (!c) return PSN_LK_ERR_ARG;
+    if (w) *w = c->src_w;
+    if (h) *h = c->src_h;
+    return PSN_LK_OK;
+}
+
+int psn_lk_scale(psn_lk_ctx *c, double *s) {
+    if (!c || !s) return PSN_LK_ERR_ARG;
+    *s = c->scale;
     return PSN_LK_OK;
 }
 
@@ -486,7 +580,7 @@ void psn_lk_destroy(psn_lk_ctx *c) {
     c->lg_retired.clear();
     for (void *p : {(void *)c->d_samples, (void *)c->d_ctr, (void *)c->d_pyr, (void *)c->d_slots, (void *)c->d_src, (void *)c->d_prev, (void *)c->d_next,
                     (void *)c->d_err, (void *)c->d_status, (void *)c->d_gf_kp, (void *)c->d_gf_cnt, (void *)c->d_gf_xy,
-                    (void *)c->d_gf_oc, (void *)c->d_gf_ot})
+                    (void *)c->d_gf_oc, (void *)c->d_gf_ot, (void *)c->d_gray, (void *)c->d_rz_tab})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)c->d_hist_rects, (void *)c->d_hist_counts})
         if (p) (void)hipFree(p);
@@ -609,10 +703,12 @@ int psn_lk_level_size(psn_lk_ctx *c, int level, int *w, int *h) {
 
 // One standalone pyramid launch of `slot` on stream s (timed when timing is
 // enabled); the slot's ready event is recorded after it.
-static int launch_build(psn_lk_ctx *c, const psn::PyrBuildArgs &a, hipStream_t s, int slot) {
+static int launch_build(psn_lk_ctx *c, const psn::PyrBuildArgs &a, hipStream_t s, int slot,
+                        const psn::ResizeArgs *rz) {
     const bool timed = c->tcap && (c->calls_push++ % c->every) == 0;
     const long ti = timed ? (c->n_push % c->tcap) : 0;
     if (timed) HIPCHK(c, hipEventRecord(c->ev_push[2 * ti], s));
+    if (rz) HIPCHK(c, psn::launch_resize_gray(*rz, s));  // a scaled context: the source into the plane `a` reads
     HIPCHK(c, psn::launch_pyramid(a, s));
     if (timed) {
         HIPCHK(c, hipEventRecord(c->ev_push[2 * ti + 1], s));
@@ -723,12 +819,64 @@ static psn::PyrBuildArgs build_args(const psn_lk_ctx *c, int slot, const uint8_t
     return a;
 }
 
-static int push_device_impl(psn_lk_ctx *c, int slot, const uint8_t *dev, int stride, int channels) {
+// The resize of a source frame into `slot`'s gray plane (a scaled context).
+static psn::ResizeArgs resize_args(const psn_lk_ctx *c, int slot, const uint8_t *dev, int stride, int channels) {
+    psn::ResizeArgs r{};
+    r.src = dev;
+    r.src_stride = stride;
+    r.channels = channels;
+    r.sw = c->src_w;
+    r.sh = c->src_h;
+    r.dst = c->d_gray + (size_t)slot * c->gray_pitch * c->height;
+    r.dst_pitch = c->gray_pitch;
+    r.dw = c->width;
+    r.dh = c->height;
+    r.xofs = c->d_rz_tab;
+    r.xcoef = (const uint32_t *)(c->d_rz_tab + c->width);
+    r.yofs = c->d_rz_tab + 2 * (size_t)c->width;
+    r.ycoef = (const uint32_t *)(c->d_rz_tab + 2 * (size_t)c->width + c->height);
+    return r;
+}
+
+// Resize (a scaled context) and pyramid build of `slot` from a source-size device frame, on stream s.
+static int ingest_build(psn_lk_ctx *c, int slot, const uint8_t *dev, int stride, int channels, hipStream_t s) {
+    if (!c->rz) return launch_build(c, build_args(c, slot, dev, stride, channels), s, slot);
+    const psn::ResizeArgs r = resize_args(c, slot, dev, stride, channels);
+    return launch_build(c, build_args(c, slot, r.dst, r.dst_pitch, 1), s, slot, &r);
+}
+
+// The resize alone, timed as a push: a fused-mode push of a scaled context (the
+// pyramid build it defers runs inside a later LK launch).
+static int launch_resize(psn_lk_ctx *c, const psn::ResizeArgs &r, hipStream_t s) {
+    const bool timed = c->tcap && (c->calls_push++ % c->every) == 0;
+    const long ti = timed ? (c->n_push % c->tcap) : 0;
+    if (timed) HIPCHK(c, hipEventRecord(c->ev_push[2 * ti], s));
+    HIPCHK(c, psn::launch_resize_gray(r, s));
+    if (timed) {
+        HIPCHK(c, hipEventRecord(c->ev_push[2 * ti + 1], s));
+        c->n_push++;
+    }
+    return PSN_LK_OK;
+}
+
+// lk_frame: the frame has the LK size already (psn_calc_optical_flow_pyr_lk's images): no resize.
+static int push_device_impl(psn_lk_ctx *c, int slot, const uint8_t *dev, int stride, int channels,
+                            bool lk_frame = false) {
     int rc = flush_pending(c);  // at most one deferred build
     if (rc) return rc;
-    const psn::PyrBuildArgs a = build_args(c, slot, dev, stride, channels);
+    const bool rz = c->rz && !lk_frame;
+    psn::ResizeArgs r{};
+    if (rz) r = resize_args(c, slot, dev, stride, channels);
+    const psn::PyrBuildArgs a = rz ? build_args(c, slot, r.dst, r.dst_pitch, 1) : build_args(c, slot, dev, stride, channels);
     c->filled[slot] = 1;
     if (c->overlap == PSN_LK_OVERLAP_FUSED && c->nlevels > 1) {
+        if (rz) {
+            // the resize runs now, on the LK stream, after the slot's last build (it
+            // read the plane, maybe on an ingest stream); only the pyramid build is
+            // deferred, and it reads the plane, not the caller's frame
+            if ((rc = wait_prev_build(c, slot, c->stream))) return rc;
+            if ((rc = launch_resize(c, r, c->stream))) return rc;
+        }
         c->ready_rec[slot] = 0;  // readers wait for the build by stream order (it runs first on the LK stream)
         c->pend = true;
         c->pend_slot = slot;
@@ -742,7 +890,7 @@ static int push_device_impl(psn_lk_ctx *c, int slot, const uint8_t *dev, int str
     if (rc) return rc;
     rc = wait_prev_build(c, slot, s);
     if (rc) return rc;
-    return launch_build(c, a, s, slot);
+    return launch_build(c, a, s, slot, rz ? &r : nullptr);
 }
 
 // The slot's staging buffer, grown to `need` bytes (the old one may still be read by the ingest stream).
@@ -764,15 +912,15 @@ int psn_lk_push_frame_jpeg(psn_lk_ctx *c, int slot, const uint8_t *jpeg, size_t 
     int w = 0, h = 0;
     int rc = psn_jpeg_info(jpeg, len, &w, &h, nullptr);
     if (rc) return set_err(c, rc, "JPEG headers");
-    if (w != c->width || h != c->height) return set_err(c, PSN_LK_ERR_ARG, "JPEG %dx%d, context %dx%d", w, h, c->width, c->height);
+    if (w != c->src_w || h != c->src_h) return set_err(c, PSN_LK_ERR_ARG, "JPEG %dx%d, context %dx%d", w, h, c->src_w, c->src_h);
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = flush_pending(c))) return rc;
     if (!c->jpeg) {
         if ((rc = psn_jpeg_create(c->device, &c->jpeg))) return set_err(c, rc, "psn_jpeg_create");
         psn_jpeg_set_stream(c->jpeg, c->ingest_stream);
     }
-    const size_t row = (size_t)c->width * 3;
-    if ((rc = ensure_stage(c, slot, row * c->height))) return rc;
+    const size_t row = (size_t)c->src_w * 3;
+    if ((rc = ensure_stage(c, slot, row * c->src_h))) return rc;
     if ((rc = wait_slot_free(c, slot, c->ingest_stream))) return rc;
     // the slot's previous build may still read d_stage[slot] (an async push builds
     // on either ingest stream): the decode overwrites it only after that build
@@ -781,16 +929,16 @@ int psn_lk_push_frame_jpeg(psn_lk_ctx *c, int slot, const uint8_t *jpeg, size_t 
     if (rc) return set_err(c, rc, "JPEG decode: %s", psn_jpeg_last_error(c->jpeg));
     c->filled[slot] = 1;
     c->color_src[slot] = {c->d_stage[slot], (int)row, 3, false, 0};
-    return launch_build(c, build_args(c, slot, c->d_stage[slot], (int)row, 3), c->ingest_stream, slot);
+    return ingest_build(c, slot, c->d_stage[slot], (int)row, 3, c->ingest_stream);
 }
 
 int psn_lk_push_frame_async(psn_lk_ctx *c, int slot, const uint8_t *host, int stride, int channels) {
-    if (!c || !host || (channels != 1 && channels != 3) || stride < c->width * channels) return PSN_LK_ERR_ARG;
+    if (!c || !host || (channels != 1 && channels != 3) || stride < c->src_w * channels) return PSN_LK_ERR_ARG;
     if (slot < 0 || slot >= c->user_slots) return set_err(c, PSN_LK_ERR_SLOT, "slot %d out of range", slot);
     HIPCHK(c, hipSetDevice(c->device));
     int rc = flush_pending(c);
     if (rc) return rc;
-    const size_t row = (size_t)c->width * channels, need = row * c->height;
+    const size_t row = (size_t)c->src_w * channels, need = row * c->src_h;
     if ((rc = ensure_stage(c, slot, need))) return rc;
     hipStream_t s = c->ingest_streams[c->ingest_rr++ % psn_lk_ctx::kIngestStreams];
     hipStream_t cs = c->copy_streams[c->copy_rr++ % psn_lk_ctx::kCopyStreams];
@@ -804,18 +952,18 @@ int psn_lk_push_frame_async(psn_lk_ctx *c, int slot, const uint8_t *host, int st
     if ((size_t)stride == row)  // contiguous rows: one linear copy (the DMA engine's fast path)
         HIPCHK(c, hipMemcpyAsync(c->d_stage[slot], host, need, hipMemcpyHostToDevice, cs));
     else
-        HIPCHK(c, hipMemcpy2DAsync(c->d_stage[slot], row, host, stride, row, c->height, hipMemcpyHostToDevice, cs));
+        HIPCHK(c, hipMemcpy2DAsync(c->d_stage[slot], row, host, stride, row, c->src_h, hipMemcpyHostToDevice, cs));
     HIPCHK(c, hipEventRecord(c->copy_done[slot], cs));
     rc = wait_slot_free(c, slot, s);
     if (rc) return rc;
     HIPCHK(c, hipStreamWaitEvent(s, c->copy_done[slot], 0));
     c->filled[slot] = 1;
     c->color_src[slot] = {c->d_stage[slot], (int)row, channels, false, 0};
-    return launch_build(c, build_args(c, slot, c->d_stage[slot], (int)row, channels), s, slot);
+    return ingest_build(c, slot, c->d_stage[slot], (int)row, channels, s);
 }
 
 int psn_lk_push_frame_device(psn_lk_ctx *c, int slot, const uint8_t *dev, int stride, int channels) {
-    if (!c || !dev || (channels != 1 && channels != 3) || stride < c->width * channels) return PSN_LK_ERR_ARG;
+    if (!c || !dev || (channels != 1 && channels != 3) || stride < c->src_w * channels) return PSN_LK_ERR_ARG;
     if (slot < 0 || slot >= c->user_slots) return set_err(c, PSN_LK_ERR_SLOT, "slot %d out of range", slot);
     HIPCHK(c, hipSetDevice(c->device));
     const int rc = push_device_impl(c, slot, dev, stride, channels);
@@ -823,8 +971,10 @@ int psn_lk_push_frame_device(psn_lk_ctx *c, int slot, const uint8_t *dev, int st
     return rc;
 }
 
-static int push_host_impl(psn_lk_ctx *c, int slot, const uint8_t *host, int stride, int channels) {
-    const size_t row = (size_t)c->width * channels, need = row * c->height;
+static int push_host_impl(psn_lk_ctx *c, int slot, const uint8_t *host, int stride, int channels,
+                          bool lk_frame = false) {
+    const int fw = lk_frame ? c->width : c->src_w, fh = lk_frame ? c->height : c->src_h;
+    const size_t row = (size_t)fw * channels, need = row * fh;
     int rc0 = flush_pending(c);  // a deferred build may still read d_src's predecessor frame
     if (rc0) return rc0;
     if (c->d_src_cap < need) {
@@ -838,8 +988,8 @@ static int push_host_impl(psn_lk_ctx *c, int slot, const uint8_t *host, int stri
     const int mode = c->overlap;
     if (mode == PSN_LK_OVERLAP_FUSED) c->overlap = PSN_LK_OVERLAP_OFF;
     hipStream_t s = c->overlap == PSN_LK_OVERLAP_STREAM ? c->ingest_stream : c->stream;
-    hipError_t ce = hipMemcpy2DAsync(c->d_src, row, host, stride, row, c->height, hipMemcpyHostToDevice, s);
-    int rc = ce == hipSuccess ? push_device_impl(c, slot, c->d_src, (int)row, channels)
+    hipError_t ce = hipMemcpy2DAsync(c->d_src, row, host, stride, row, fh, hipMemcpyHostToDevice, s);
+    int rc = ce == hipSuccess ? push_device_impl(c, slot, c->d_src, (int)row, channels, lk_frame)
                               : set_err(c, PSN_LK_ERR_HIP, "hipMemcpy2DAsync: %s", hipGetErrorString(ce));
     c->overlap = mode;
     c->src_gen++;  // d_src holds this frame now: the colour source of earlier host pushes is gone
@@ -850,7 +1000,7 @@ static int push_host_impl(psn_lk_ctx *c, int slot, const uint8_t *host, int stri
 }
 
 int psn_lk_push_frame(psn_lk_ctx *c, int slot, const uint8_t *host, int stride, int channels) {
-    if (!c || !host || (channels != 1 && channels != 3) || stride < c->width * channels) return PSN_LK_ERR_ARG;
+    if (!c || !host || (channels != 1 && channels != 3) || stride < c->src_w * channels) return PSN_LK_ERR_ARG;
     if (slot < 0 || slot >= c->user_slots) return set_err(c, PSN_LK_ERR_SLOT, "slot %d out of range", slot);
     HIPCHK(c, hipSetDevice(c->device));
     return push_host_impl(c, slot, host, stride, channels);
@@ -1472,9 +1622,9 @@ int psn_calc_optical_flow_pyr_lk(psn_lk_ctx *c, const uint8_t *prev_img, const u
     if (!prev_pts || !next_pts || !status) return PSN_LK_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     const int sa = c->user_slots, sb = c->user_slots + 1;
-    int rc = push_host_impl(c, sa, prev_img, stride, 1);
+    int rc = push_host_impl(c, sa, prev_img, stride, 1, true);
     if (rc) return rc;
-    rc = push_host_impl(c, sb, next_img, stride, 1);
+    rc = push_host_impl(c, sb, next_img, stride, 1, true);
     if (rc) return rc;
     psn_lk_query q;
     q.prev_slot = sa;
@@ -1807,8 +1957,8 @@ int psn_lk_box_histograms(psn_lk_ctx *c, int nset, const int *slots, const int *
             long long x = r[0], y = r[1], w = r[2], h = r[3];
             if (x < 0) x = 0;
             if (y < 0) y = 0;
-            if (x + w > c->width) w = c->width - x;
-            if (y + h > c->height) h = c->height - y;
+            if (x + w > c->src_w) w = c->src_w - x;  // (the colour frame has the source size)
+            if (y + h > c->src_h) h = c->src_h - y;
             if (w <= 0 || h <= 0) x = y = w = h = 0;  // an empty crop
             c->h_hist_rects[k] = psn_rgbhist_rect{cs.p, cs.stride, (int)x, (int)y, (int)w, (int)h};
             bands = std::max(bands, psn::rgbhist_bands((int)w, (int)h));

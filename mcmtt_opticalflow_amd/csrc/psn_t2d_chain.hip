@@ -6,10 +6,11 @@
 // LocalSearchKLT, step by step (the host version is
 // mcmtt_opticalflow_amd/host/tracker2d_flow.cpp):
 //   1. d_i = nextPts_i - prevPts_i in float, widened to double; a vector
-//      "moves" unless |d_i| < 0.1 (:477-490);
+//      "moves" unless |d_i| < 0.1 * scale (:477-490);
 //   2. fewer than half moving -> the box stays, no inliers (:493-496);
 //   3. sort dx and dy (:499-500); the mode of each is the first sorted value
-//      with the most neighbours closer than window = 0.2 * box.w (:502-537);
+//      with the most neighbours closer than window = box.w * 0.2 * scale (:502-537;
+//      the box is the scaled one already: the reference applies the scale twice);
 //   4. inliers = moving vectors within `window` of the mode, in point order
 //      (:540-546); box += mode (:549-553).
 // Ordered compactions are lane-ordered prefix sums, the sort a bitonic
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(kLanes) void chain_step_kernel(psn_t2d_chain_dev C,
         const float dyf = C.nxt[pb + 2 * t + 1] - C.cur[pb + 2 * t + 1];
         mx = (double)dxf;
         my = (double)dyf;
-        moving = !(sqrt(mx * mx + my * my) < 0.1 * 1.0);
+        moving = !(sqrt(mx * mx + my * my) < 0.1 * C.scale);
     }
     const int pos = block_incl_scan(moving ? 1 : 0, tmp);
     __shared__ int nmov;
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(kLanes) void chain_step_kernel(psn_t2d_chain_dev C,
         __syncthreads();
         bitonic128(sdx);
         bitonic128(sdy);
-        const double ws = bw * 0.2 * 1.0;
+        const double ws = bw * 0.2 * C.scale;
         int nx = 0, ny = 0;
         if (t < M) {
             const double vx = sdx[t], vy = sdy[t];
@@ -257,7 +258,8 @@ extern "C" int psn_t2d_chain_begin_device(const psn_t2d_chain_dev *c, int min_co
 }
 
 extern "C" int psn_t2d_chain_step_device(const psn_t2d_chain_dev *c, int step, void *stream) {
-    if (!c || c->ndet < 0 || c->cap <= 0 || c->cap > 128 || step < 1 || step >= PSN_T2D_CHAIN_STEPS)
+    if (!c || c->ndet < 0 || c->cap <= 0 || c->cap > 128 || step < 1 || step >= PSN_T2D_CHAIN_STEPS ||
+        !(c->scale > 0.0))
         return PSN_LK_ERR_ARG;
     if (c->ndet == 0) return PSN_LK_OK;
     hipLaunchKernelGGL(psn::chain_step_kernel, dim3(c->ndet), dim3(psn::kLanes), 0, (hipStream_t)stream, *c, step);

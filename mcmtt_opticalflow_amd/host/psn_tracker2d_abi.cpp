@@ -233,7 +233,13 @@ double psn_t2d_box_matching_cost(psn_rect a, psn_rect b) { return psn::BoxMatchi
 
 int psn_t2d_local_search_klt(psn_rect pre_box, const float *pre_xy, const float *cur_xy, int n, psn_rect *out_box,
                              int *inlier_idx, int *n_inliers) {
-    if (n < 0 || (n > 0 && (!pre_xy || !cur_xy)) || !out_box || !n_inliers || (n > 0 && !inlier_idx))
+    return psn_t2d_local_search_klt_scaled(pre_box, pre_xy, cur_xy, n, 1.0, out_box, inlier_idx, n_inliers);
+}
+
+int psn_t2d_local_search_klt_scaled(psn_rect pre_box, const float *pre_xy, const float *cur_xy, int n, double scale,
+                                    psn_rect *out_box, int *inlier_idx, int *n_inliers) {
+    if (n < 0 || (n > 0 && (!pre_xy || !cur_xy)) || !out_box || !n_inliers || (n > 0 && !inlier_idx) ||
+        !(scale > 0.0) || !(scale <= 1.0))
         return PSN_LK_ERR_ARG;
     std::vector<psn::Point2f> pre((size_t)n), cur((size_t)n);
     for (int i = 0; i < n; i++) {
@@ -241,18 +247,22 @@ int psn_t2d_local_search_klt(psn_rect pre_box, const float *pre_xy, const float 
         cur[(size_t)i] = psn::Point2f{cur_xy[2 * i], cur_xy[2 * i + 1]};
     }
     std::vector<size_t> inl;
-    *out_box = from_rect(psn::LocalSearchKLT(to_rect(pre_box), pre, cur, inl));
+    *out_box = from_rect(psn::LocalSearchKLT(to_rect(pre_box), pre, cur, inl, scale));
     for (size_t i = 0; i < inl.size(); i++) inlier_idx[i] = (int)inl[i];
     *n_inliers = (int)inl.size();
     return 0;
 }
 
 int psn_t2d_create(int device, unsigned cam_id, int width, int height, psn_t2d **out) {
+    return psn_t2d_create_scaled(device, cam_id, width, height, 1.0, out);
+}
+
+int psn_t2d_create_scaled(int device, unsigned cam_id, int width, int height, double scale, psn_t2d **out) {
     if (!out) return PSN_LK_ERR_ARG;
     *out = nullptr;
     psn_t2d *t = new (std::nothrow) psn_t2d();
     if (!t) return PSN_LK_ERR_NOMEM;
-    const int rc = t->flow.Initialize(cam_id, width, height, device);
+    const int rc = t->flow.Initialize(cam_id, width, height, device, scale);
     if (rc) {
         delete t;
         return rc;
@@ -463,11 +473,16 @@ int psn_t2d_matching_and_updating(const psn_t2d_detection *dets, int ndet, const
 // ---- psn_t2d_group: CPSNWhere_Tracker2D::Run of several cameras ----
 
 int psn_t2d_group_create(int device, int ncams, const unsigned *cam_ids, int width, int height, psn_t2d_group **out) {
+    return psn_t2d_group_create_scaled(device, ncams, cam_ids, width, height, 1.0, out);
+}
+
+int psn_t2d_group_create_scaled(int device, int ncams, const unsigned *cam_ids, int width, int height, double scale,
+                                psn_t2d_group **out) {
     if (!out || ncams <= 0 || !cam_ids) return PSN_LK_ERR_ARG;
     *out = nullptr;
     psn_t2d_group *g = new (std::nothrow) psn_t2d_group();
     if (!g) return PSN_LK_ERR_NOMEM;
-    const int rc = g->flow.InitializeCameras(std::vector<unsigned>(cam_ids, cam_ids + ncams), width, height, device);
+    const int rc = g->flow.InitializeCameras(std::vector<unsigned>(cam_ids, cam_ids + ncams), width, height, device, scale);
     if (rc) {
         delete g;
         return rc;

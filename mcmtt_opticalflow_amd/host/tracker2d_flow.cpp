@@ -21,7 +21,7 @@ namespace psn {
 // the box shift and the inliers are the moving vectors within that window of
 // the mode, in point order.
 Rect LocalSearchKLT(Rect preBox, const std::vector<Point2f> &preFeatures, const std::vector<Point2f> &curFeatures,
-                    std::vector<size_t> &inlierFeatureIndex) {
+                    std::vector<size_t> &inlierFeatureIndex, double scale) {
     const double kMinMovement = 0.1, kNeighborRatio = 0.2;
     const size_t numFeatures = preFeatures.size();
     size_t numMoving = 0;
@@ -33,7 +33,7 @@ Rect LocalSearchKLT(Rect preBox, const std::vector<Point2f> &preFeatures, const 
         // cv::Point2f difference (float), then widened to PSN_Point2D
         const Point2f d{curFeatures[i].x - preFeatures[i].x, curFeatures[i].y - preFeatures[i].y};
         const Point2D mv(d);
-        if (mv.norm_L2() < kMinMovement * kFlowScale) continue;
+        if (mv.norm_L2() < kMinMovement * scale) continue;
         vecMoving.push_back(mv);
         vecMovingIdx.push_back(i);
         vecDx.push_back(mv.x);
@@ -43,7 +43,7 @@ Rect LocalSearchKLT(Rect preBox, const std::vector<Point2f> &preFeatures, const 
     if ((double)numMoving < (double)numFeatures * 0.5) return preBox;
     std::sort(vecDx.begin(), vecDx.end());
     std::sort(vecDy.begin(), vecDy.end());
-    const double windowSize = preBox.w * kNeighborRatio * kFlowScale;
+    const double windowSize = preBox.w * kNeighborRatio * scale;
     size_t maxX = 0, maxY = 0;
     Point2D est(0.0, 0.0);
     // neighbour counts |v[d] - v[c]| < windowSize of every d. On sorted finite
@@ -122,21 +122,28 @@ int Tracker2DFlow::fail(int rc, const char *what) {
     return rc;
 }
 
-int Tracker2DFlow::Initialize(unsigned camID, int width, int height, int device) {
-    return InitializeCameras(std::vector<unsigned>{camID}, width, height, device);
+int Tracker2DFlow::Initialize(unsigned camID, int width, int height, int device, double scale) {
+    return InitializeCameras(std::vector<unsigned>{camID}, width, height, device, scale);
 }
 
-int Tracker2DFlow::InitializeCameras(const std::vector<unsigned> &camIDs, int width, int height, int device) {
+int Tracker2DFlow::InitializeCameras(const std::vector<unsigned> &camIDs, int width, int height, int device,
+                                     double scale) {
     Finalize();
     if (camIDs.empty() || width <= 0 || height <= 0) return PSN_LK_ERR_ARG;
+    if (psn_lk_scaled_size(width, height, scale, &lk_w_, &lk_h_)) {
+        err_ = "scale outside (0, 1] or a scaled frame below 1 px";
+        return PSN_LK_ERR_ARG;
+    }
     width_ = width;
     height_ = height;
+    scale_ = scale;
     const int nslots = (int)camIDs.size() * kSlotsPerCam;
     // full pyramids of every camera's slots; the reference's default maxLevel 3 needs 4 levels
-    const int rc = psn_lk_create(device, width, height, nslots, 3, &lk_);
+    // (at scale 1.0 psn_lk_create's context: no resize launch)
+    const int rc = psn_lk_create_scaled(device, width, height, scale, nslots, 3, &lk_);
     if (rc) {
         lk_ = nullptr;
-        err_ = "psn_lk_create failed (" + std::to_string(rc) + ")";
+        err_ = "psn_lk_create_scaled failed (" + std::to_string(rc) + ")";
         return rc;
     }
     cams_.assign(camIDs.size(), Cam());
@@ -560,7 +567,7 @@ int Tracker2DFlow::PassLaunchChains(std::vector<PassCam> &pc, bool gridfast, uin
         ci.k0[p.cam] = p.k0;
         ci.ndet[p.cam] = p.dets->size();
         for (size_t i = 0; i < p.dets->size(); i++) {
-            const Rect box = (*p.dets)[i].box.scale(kFlowScale);
+            const Rect box = (*p.dets)[i].box.scale(scale_);
             ci.win[p.k0 + i] = {(int)(box.w * kWinSizeRatio), (int)(box.h * kWinSizeRatio)};
         }
     }
@@ -590,7 +597,7 @@ int Tracker2DFlow::PassLaunchChains(std::vector<PassCam> &pc, bool gridfast, uin
             const int steps = StepsAvailable(p.cam);
             for (size_t i = 0; i < p.dets->size(); i++) {
                 const size_t k = p.k0 + i;
-                const Rect box = (*p.dets)[i].box.scale(kFlowScale);
+                const Rect box = (*p.dets)[i].box.scale(scale_);
                 b.h_boxes[4 * k] = box.x;
                 b.h_boxes[4 * k + 1] = box.y;
                 b.h_boxes[4 * k + 2] = box.w;
@@ -617,7 +624,7 @@ int Tracker2DFlow::PassLaunchChains(std::vector<PassCam> &pc, bool gridfast, uin
                 nrois.push_back((int)n);
                 for (size_t i = 0; i < n; i++) {
                     // cv::Rect((int)x, (int)y, (int)w, (int)h) of the cropped, scaled box
-                    const Rect r = (*p.dets)[i].box.scale(kFlowScale).cropWithSize(width_, height_);
+                    const Rect r = (*p.dets)[i].box.scale(scale_).cropWithSize(lk_w_, lk_h_);
                     const size_t k = p.k0 + i;
                     rois[4 * k] = (int)r.x;
                     rois[4 * k + 1] = (int)r.y;
@@ -673,6 +680,7 @@ int Tracker2DFlow::PassLaunchChains(std::vector<PassCam> &pc, bool gridfast, uin
         cd.set_cnt = rv.setcnt;
         cd.nsteps = rv.nsteps;
         cd.last_step = db.d_last;
+        cd.scale = scale_;
         // cleared counters, set 0 = the features at t, the feature-minimum gate: one launch
         if (!rc) rc = psn_t2d_chain_begin_device(&cd, (int)kT2dMinFeatures, st);
         if (rc) return rc;
@@ -985,7 +993,7 @@ void Tracker2DFlow::PassUnpack(std::vector<PassCam> &pc) {
             const int ns = hv.nsteps[k];
             for (int s2 = 1; s2 <= ns; s2++) {
                 const double *r = hv.obox + (k * S + s2) * 4;
-                ob.boxes.push_back(Rect(r[0], r[1], r[2], r[3]).scale(1.0 / kFlowScale));
+                ob.boxes.push_back(Rect(r[0], r[1], r[2], r[3]).scale(1.0 / scale_));
             }
             for (int r = 0; ns > 0 && r <= ns; r++) {
                 const int m = hv.setcnt[k * S + r];
@@ -1112,7 +1120,7 @@ int Tracker2DFlow::DetectFeatures(const std::vector<Detection> &dets, uint32_t s
     std::vector<int> rois(4 * n), cnt(n), tot(n);
     for (size_t i = 0; i < n; i++) {
         // cv::Rect((int)x, (int)y, (int)w, (int)h) of the cropped, scaled box
-        const Rect r = dets[i].box.scale(kFlowScale).cropWithSize(width_, height_);
+        const Rect r = dets[i].box.scale(scale_).cropWithSize(lk_w_, lk_h_);
         rois[4 * i] = (int)r.x;
         rois[4 * i + 1] = (int)r.y;
         rois[4 * i + 2] = (int)r.w;
@@ -1219,7 +1227,7 @@ void Tracker2DFlow::BackwardJobs(int step, std::vector<Chain> &chains, const std
                                  std::vector<Job> &jobs) {
     for (Chain &c : chains) {
         if (!c.active) continue;
-        const Rect box = out[c.obj].detection.box.scale(kFlowScale);
+        const Rect box = out[c.obj].detection.box.scale(scale_);
         const int win = (int)(box.w * kWinSizeRatio);  // square window of the box width (:782)
         jobs.push_back(Job{cams_[0].ring[kT2dInterval - step], cams_[0].ring[kT2dInterval - 1 - step], win, win, &c.curr,
                            &c.prev, &c.status});
@@ -1232,12 +1240,12 @@ void Tracker2DFlow::BackwardStepDone(std::vector<Chain> &chains, std::vector<Det
         if (!c.active) continue;
         DetectedObject &o = out[c.obj];
         // status is ignored: every nextPts value feeds LocalSearchKLT (:787)
-        const Rect newRect = LocalSearchKLT(o.detection.box.scale(kFlowScale), c.curr, c.prev, inl);
+        const Rect newRect = LocalSearchKLT(o.detection.box.scale(scale_), c.curr, c.prev, inl, scale_);
         if (inl.size() < kT2dMinFeatures) {  // :788
             c.active = false;
             continue;
         }
-        o.boxes.push_back(newRect.scale(1.0 / kFlowScale));
+        o.boxes.push_back(newRect.scale(1.0 / scale_));
         if (o.vecvecTrackedFeatures.empty()) {
             std::vector<Point2f> cur;
             for (size_t k : inl) cur.push_back(c.curr[k]);
@@ -1305,7 +1313,7 @@ void Tracker2DFlow::ForwardJobs(size_t cam, const std::vector<Tracker2D *> &trac
     for (size_t t = 0; t < trackers.size(); t++) {
         Tracker2D *tr = trackers[t];
         tr->trackedPoints.clear();
-        const Rect cur = tr->boxes.back().scale(kFlowScale);
+        const Rect cur = tr->boxes.back().scale(scale_);
         jobs.push_back(Job{ring[kT2dInterval - 2], ring[kT2dInterval - 1], (int)(cur.w * kWinSizeRatio),
                            (int)(cur.h * kWinSizeRatio), &tr->featurePoints, &tr->trackedPoints, &status[t]});
     }
@@ -1328,8 +1336,8 @@ void Tracker2DFlow::ForwardDone(const std::vector<Tracker2D *> &trackers, std::v
             vCurr.push_back(tr->trackedPoints[i]);
         }
         if (vCurr.size() < kT2dMinFeatures) continue;  // :889 (featurePoints kept, trackedPoints = raw output)
-        Rect newBox = LocalSearchKLT(tr->boxes.back().scale(kFlowScale), vPrev, vCurr, inl);
-        newBox = newBox.scale(1.0 / kFlowScale);
+        Rect newBox = LocalSearchKLT(tr->boxes.back().scale(scale_), vPrev, vCurr, inl, scale_);
+        newBox = newBox.scale(1.0 / scale_);
         tr->boxes.push_back(newBox);
         tr->heads.push_back(tr->heads.empty() ? Rect() : tr->heads.back());
         for (size_t d = 0; d < D; d++) {
@@ -1642,7 +1650,7 @@ int Tracker2DFlow::RunComplete(std::vector<CamFrame> &io, std::vector<CamFrame> 
     // reference) fails the frame before any camera is updated
     for (size_t c = 0; c < cams_.size(); c++)
         for (const Tracker2D *tr : cams_[c].trackers) {
-            const Rect b = tr->boxes.back().scale(kFlowScale);
+            const Rect b = tr->boxes.back().scale(scale_);
             const int we = forward_window_error((int)(b.w * kWinSizeRatio), (int)(b.h * kWinSizeRatio));
             if (we) {
                 err_ = "camera " + std::to_string(c) + ": tracker " + std::to_string(tr->id) + " forward window";

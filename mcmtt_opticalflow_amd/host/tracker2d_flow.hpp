@@ -32,11 +32,15 @@ constexpr int kSlotsPerCam = kT2dInterval + kT2dStaging;
 constexpr size_t kT2dMinFeatures = 4;    // PSN_2D_FEATURE_MIN_NUM_TRACK (:12)
 constexpr size_t kT2dMaxFeatures = 100;  // PSN_2D_FEATURE_MAX_NUM_TRACK (:13)
 constexpr int kT2dResBlocks = 3;         // chain result blocks used in turn by consecutive passes
-constexpr double kFlowScale = 1.0;       // PSN_2D_OPTICALFLOW_SCALE (:18)
+// PSN_2D_OPTICALFLOW_SCALE (:18) is a runtime value here: Tracker2DFlow's scale,
+// the `scale` argument of LocalSearchKLT (a product with a runtime 1.0 is exact,
+// so one code path serves both of the reference's builds)
 constexpr double kWinSizeRatio = 1.0;    // PSN_2D_FEATURE_WIN_SIZE_RATIO (:15)
 
+// preBox is the box already scaled; scale enters the minimum movement (:481) and,
+// a second time, the neighbour window (:502), as in the reference
 Rect LocalSearchKLT(Rect preBox, const std::vector<Point2f> &preFeatures, const std::vector<Point2f> &curFeatures,
-                    std::vector<size_t> &inlierFeatureIndex);
+                    std::vector<size_t> &inlierFeatureIndex, double scale = 1.0);
 double BoxMatchingCost(const Rect &box1, const Rect &box2);
 void ResultWithTracker(const Tracker2D &tracker, Object2DInfo &out);
 // tracker2d_match.cpp: the assignment of Track2D_MatchingAndUpdating (inf
@@ -56,15 +60,18 @@ class Tracker2DFlow {
     Tracker2DFlow(const Tracker2DFlow &) = delete;
     Tracker2DFlow &operator=(const Tracker2DFlow &) = delete;
 
-    int Initialize(unsigned camID, int width, int height, int device);  // one camera
-    int InitializeCameras(const std::vector<unsigned> &camIDs, int width, int height, int device);
+    // width x height: the frames' (source) size; scale in (0, 1]: the whole flow
+    // path -- ring, GridFAST rois, LK windows, LocalSearchKLT -- runs at
+    // (int)(width * scale) x (int)(height * scale), boxes come back with 1 / scale
+    int Initialize(unsigned camID, int width, int height, int device, double scale = 1.0);  // one camera
+    int InitializeCameras(const std::vector<unsigned> &camIDs, int width, int height, int device, double scale = 1.0);
     void Finalize();
     size_t NumCameras() const { return cams_.size(); }
     psn_lk_ctx *LkContext() const { return lk_; }
 
     // ---- single-camera flow-stage API (camera 0), the reference's call order:
     // PushFrame (frame t into the newest ring slot), the steps, RotateRing ----
-    int PushFrame(const uint8_t *frame, int stride, int channels);  // cvtColor(BGR2GRAY) + resize 1.0
+    int PushFrame(const uint8_t *frame, int stride, int channels);  // cvtColor(BGR2GRAY) + resize(scale)
     int PushFrameDevice(const uint8_t *dev, int stride, int channels);  // frame already in device memory
     void RotateRing();  // buffer circulation at the end of Run
     // Feature extraction of the backward chain (:734-757) on frame t (the
@@ -132,6 +139,7 @@ class Tracker2DFlow {
     int SlotOfFrame(size_t cam, unsigned frameIdx, int *slot);
     int Width() const { return width_; }
     int Height() const { return height_; }
+    double Scale() const { return scale_; }
     // diagnostic: accumulated host microseconds from RunComplete's entry to its
     // phases (copies + next chains enqueued, device done, unpacked, matched, next
     // forward enqueued) and the number of RunComplete calls; reset on read
@@ -264,7 +272,9 @@ class Tracker2DFlow {
     void SyncChains();
     std::vector<psn_lk_query> fwd_queries_;
     std::vector<Cam> cams_;
-    int width_ = 0, height_ = 0;
+    int width_ = 0, height_ = 0;  // frame (source) size
+    int lk_w_ = 0, lk_h_ = 0;     // the LK context's size: the frame at scale_
+    double scale_ = 1.0;
     std::vector<char> filled_;  // per LK slot
     std::string err_;
     // batched-call staging

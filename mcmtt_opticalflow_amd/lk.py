@@ -57,19 +57,49 @@ def effective_max_level(width, height, win_w, win_h, max_level) -> int:
     return _lib.load().psn_lk_effective_max_level(width, height, win_w, win_h, max_level)
 
 
+def scaled_size(width: int, height: int, scale: float):
+    """psn_lk_scaled_size: the LK size (lw, lh) of a width x height source at `scale`."""
+    lw, lh = ctypes.c_int(), ctypes.c_int()
+    rc = _lib.load().psn_lk_scaled_size(int(width), int(height), float(scale), ctypes.byref(lw), ctypes.byref(lh))
+    if rc != 0:
+        raise PsnLkError(rc, f"psn_lk_scaled_size({width}, {height}, {scale})")
+    return lw.value, lh.value
+
+
+def resize_plan(src: int, dst: int, is_x: bool):
+    """psn_lk_resize_plan: (ofs (dst,) int32, coef (dst, 2) int16) of one axis of the ingest resize."""
+    ofs = np.zeros(max(dst, 1), np.int32)
+    coef = np.zeros((max(dst, 1), 2), np.int16)
+    rc = _lib.load().psn_lk_resize_plan(int(src), int(dst), ofs.ctypes.data, coef.ctypes.data, int(bool(is_x)))
+    if rc != 0:
+        raise PsnLkError(rc, f"psn_lk_resize_plan({src}, {dst})")
+    return ofs[:dst], coef[:dst]
+
+
 class LKContext:
-    """One camera: device ring of `ring_slots` pyramids (max_level_cap+1 levels)."""
+    """One camera: device ring of `ring_slots` pyramids (max_level_cap+1 levels).
+
+    width x height is the size of pushed frames. scale (PSN_2D_OPTICALFLOW_SCALE,
+    None = psn_lk_create, i.e. 1.0): a double in (0, 1]; the ring, LK queries and
+    GridFAST rois then live at the LK size (lk_width x lk_height), to which every
+    pushed frame is resized on the device (psn_lk_create_scaled)."""
 
     def __init__(self, width: int, height: int, ring_slots: int = 4, max_level_cap: int = 3, device: int = 0,
-                 variants: dict | None = None):
+                 variants: dict | None = None, scale: float | None = None):
         self._L = _lib.load()
         self.width, self.height = width, height
         self.ring_slots, self.max_level_cap = ring_slots, max_level_cap
         h = ctypes.c_void_p()
-        rc = self._L.psn_lk_create(device, width, height, ring_slots, max_level_cap, ctypes.byref(h))
+        if scale is None:
+            rc = self._L.psn_lk_create(device, width, height, ring_slots, max_level_cap, ctypes.byref(h))
+        else:
+            rc = self._L.psn_lk_create_scaled(device, width, height, float(scale), ring_slots, max_level_cap,
+                                              ctypes.byref(h))
         if rc != 0:
-            raise PsnLkError(rc, "psn_lk_create")
+            raise PsnLkError(rc, "psn_lk_create" if scale is None else f"psn_lk_create_scaled(scale={scale})")
         self._h = h
+        self.scale = self.get_scale() if hasattr(self._L, "psn_lk_scale") else 1.0  # (an A/B experiment's older build)
+        self.lk_width, self.lk_height = self.level_size(0)
         for k, v in (variants or {}).items():
             self.set_variant(k, v)
 
@@ -105,6 +135,22 @@ class LKContext:
     def set_stream(self, stream_ptr: int | None):
         self._check(self._L.psn_lk_set_stream(self._h, stream_ptr), "set_stream")
 
+    def level_size(self, level: int):
+        w, h = ctypes.c_int(), ctypes.c_int()
+        self._check(self._L.psn_lk_level_size(self._h, level, ctypes.byref(w), ctypes.byref(h)), "level_size")
+        return w.value, h.value
+
+    def source_size(self):
+        """psn_lk_source_size: the size of pushed frames."""
+        w, h = ctypes.c_int(), ctypes.c_int()
+        self._check(self._L.psn_lk_source_size(self._h, ctypes.byref(w), ctypes.byref(h)), "source_size")
+        return w.value, h.value
+
+    def get_scale(self) -> float:
+        s = ctypes.c_double()
+        self._check(self._L.psn_lk_scale(self._h, ctypes.byref(s)), "scale")
+        return s.value
+
     def set_ingest_overlap(self, mode=True):
         """Ingest overlap mode: False/0 off, True/1 internal ingest stream, 2 fused
         into the next LK launch's tail (see psn_lk_set_ingest_overlap)."""
@@ -128,7 +174,7 @@ class LKContext:
                     "push_frame_async")
 
     def push_frame_jpeg(self, slot: int, data: bytes):
-        """A baseline JPEG of the context's size, decoded on the device (psn_lk_push_frame_jpeg)."""
+        """A baseline JPEG of the context's (source) size, decoded on the device (psn_lk_push_frame_jpeg)."""
         buf = ctypes.create_string_buffer(bytes(data), len(data))
         self._check(self._L.psn_lk_push_frame_jpeg(self._h, slot, buf, len(data)), "push_frame_jpeg")
 

@@ -151,6 +151,11 @@ def load():
     L.psn_t2d_box_matching_cost.restype = ctypes.c_double
     L.psn_t2d_local_search_klt.argtypes = [Rect, fp, fp, ip, ctypes.POINTER(Rect), vp, ctypes.POINTER(ip)]
     L.psn_t2d_create.argtypes = [ip, ctypes.c_uint, ip, ip, ctypes.POINTER(vp)]
+    if hasattr(L, "psn_t2d_create_scaled"):  # (absent from the A/B experiments' older builds only)
+        L.psn_t2d_local_search_klt_scaled.argtypes = [Rect, fp, fp, ip, ctypes.c_double, ctypes.POINTER(Rect), vp,
+                                                      ctypes.POINTER(ip)]
+        L.psn_t2d_create_scaled.argtypes = [ip, ctypes.c_uint, ip, ip, ctypes.c_double, ctypes.POINTER(vp)]
+        L.psn_t2d_group_create_scaled.argtypes = [ip, ip, vp, ip, ip, ctypes.c_double, ctypes.POINTER(vp)]
     L.psn_t2d_destroy.argtypes = [vp]
     L.psn_t2d_destroy.restype = None
     L.psn_t2d_last_error.argtypes = [vp]
@@ -250,15 +255,21 @@ def unpack_appearance(slot: np.ndarray, cap: int = 64):
     return cam.value, frame.value, [arr[i].to_dict() for i in range(n.value)]
 
 
-def local_search_klt(pre_box, pre: np.ndarray, cur: np.ndarray):
-    """LocalSearchKLT (PSNWhere_Tracker2D.cpp:455-554) -> (box tuple, inlier indices)."""
+def local_search_klt(pre_box, pre: np.ndarray, cur: np.ndarray, scale: float | None = None):
+    """LocalSearchKLT (PSNWhere_Tracker2D.cpp:455-554) -> (box tuple, inlier indices).
+    scale: PSN_2D_OPTICALFLOW_SCALE (psn_t2d_local_search_klt_scaled; pre_box and the
+    points are in the scaled frame); None = 1.0 through psn_t2d_local_search_klt."""
     pre = np.ascontiguousarray(pre, np.float32).reshape(-1, 2)
     cur = np.ascontiguousarray(cur, np.float32).reshape(-1, 2)
     n = len(pre)
     idx = np.zeros(max(n, 1), np.int32)
     out, ni = Rect(), ctypes.c_int()
-    rc = load().psn_t2d_local_search_klt(rect(*pre_box), pre.ctypes.data, cur.ctypes.data, n, ctypes.byref(out),
-                                         idx.ctypes.data, ctypes.byref(ni))
+    if scale is None:
+        rc = load().psn_t2d_local_search_klt(rect(*pre_box), pre.ctypes.data, cur.ctypes.data, n, ctypes.byref(out),
+                                             idx.ctypes.data, ctypes.byref(ni))
+    else:
+        rc = load().psn_t2d_local_search_klt_scaled(rect(*pre_box), pre.ctypes.data, cur.ctypes.data, n, float(scale),
+                                                    ctypes.byref(out), idx.ctypes.data, ctypes.byref(ni))
     if rc:
         raise T2dError(rc, "local_search_klt")
     return out.tuple(), idx[:ni.value].tolist()
@@ -301,16 +312,23 @@ def points(arr, n) -> np.ndarray:
 
 
 class FlowTracker:
-    """One camera's Tracker2D flow stage (psn_t2d)."""
+    """One camera's Tracker2D flow stage (psn_t2d). width x height: the pushed frames.
+    scale: PSN_2D_OPTICALFLOW_SCALE in (0, 1] (psn_t2d_create_scaled): the flow path runs
+    in the frame resized by it, boxes stay in source coordinates, feature points in the
+    resized frame's; None = 1.0 through psn_t2d_create."""
 
-    def __init__(self, width: int, height: int, cam_id: int = 0, device: int = 0):
+    def __init__(self, width: int, height: int, cam_id: int = 0, device: int = 0, scale: float | None = None):
         self._L = load()
         h = ctypes.c_void_p()
-        rc = self._L.psn_t2d_create(device, cam_id, width, height, ctypes.byref(h))
+        if scale is None:
+            rc = self._L.psn_t2d_create(device, cam_id, width, height, ctypes.byref(h))
+        else:
+            rc = self._L.psn_t2d_create_scaled(device, cam_id, width, height, float(scale), ctypes.byref(h))
         if rc:
-            raise T2dError(rc, "psn_t2d_create")
+            raise T2dError(rc, "psn_t2d_create" if scale is None else f"psn_t2d_create_scaled(scale={scale})")
         self._h = h
         self.width, self.height = width, height
+        self.scale = 1.0 if scale is None else float(scale)
 
     def _check(self, rc, what):
         if rc:
@@ -450,16 +468,24 @@ def matching_and_updating(dets: list[Detection], trackers: list[Tracker], cost, 
 
 class Group:
     """psn_t2d_group: CPSNWhere_Tracker2D::Run of C cameras on one device,
-    every camera's LK work batched into the same launches."""
+    every camera's LK work batched into the same launches. scale: as FlowTracker's
+    (psn_t2d_group_create_scaled; None = 1.0 through psn_t2d_group_create)."""
 
-    def __init__(self, width: int, height: int, cam_ids, device: int = 0, max_objects: int = 64):
+    def __init__(self, width: int, height: int, cam_ids, device: int = 0, max_objects: int = 64,
+                 scale: float | None = None):
         self._L = load()
         ids = (ctypes.c_uint * len(cam_ids))(*cam_ids)
         h = ctypes.c_void_p()
-        rc = self._L.psn_t2d_group_create(device, len(cam_ids), ids, width, height, ctypes.byref(h))
+        if scale is None:
+            rc = self._L.psn_t2d_group_create(device, len(cam_ids), ids, width, height, ctypes.byref(h))
+        else:
+            rc = self._L.psn_t2d_group_create_scaled(device, len(cam_ids), ids, width, height, float(scale),
+                                                     ctypes.byref(h))
         if rc:
-            raise T2dError(rc, "psn_t2d_group_create")
+            raise T2dError(rc, "psn_t2d_group_create" if scale is None else
+                           f"psn_t2d_group_create_scaled(scale={scale})")
         self._h = h
+        self.scale = 1.0 if scale is None else float(scale)
         self.ncams = len(cam_ids)
         self.width, self.height = width, height
         self.results = [ResultBuffers(max_objects, 1) for _ in range(self.ncams)]

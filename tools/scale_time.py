@@ -1,0 +1,223 @@
+"""What the reduced optical-flow scale (PSN_2D_OPTICALFLOW_SCALE, t2d.Group(scale=))
+buys: two Tracker2D Runs, each at scale 1.0 and 0.5, each in its own process:
+
+  4k     3840 x 2160, 4 cameras, 8 boxes of 128 x 320
+  pets   1920 x 1080, 4 cameras, 8 boxes of the PETS mix (synth.pets_box_sizes)
+
+Frames are BGR and already in device memory (psn_t2d_group_push_frame_device);
+the driver is bench.tracker_run's pipelined one (launch t, push t+2,
+complete_next(t -> t+1)); features are given (the scene's points, times the
+scale: feature points live in the resized frame). Per run: camera-frames/s over
+the timed steps, then, from extra steps with psn_lk_enable_timing on, the kernel
+class of every LK launch (psn_lk_timing_launches) with its mean device time.
+
+The resize launch alone (resize_gray_kernel), per shape: HIP events around one
+psn_lk_push_frame_device of a scaled context in FUSED mode (the push enqueues
+the resize only; its pyramid build is deferred and flushed outside the events),
+mean and median of `--reps` single launches, the empty event pair's own time,
+and the achieved GB/s over source bytes read + plane bytes written. The plane
+is checked against tests/resize_ref.py first.
+
+usage: python tools/scale_time.py [--out profiles/scale_time.json] [--steps N] [--warmup N] [--reps N]
+"""
+import argparse
+import ctypes
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+RUNS = {"4k": dict(width=3840, height=2160, cameras=4, boxes=8, box_dist="uniform"),
+        "pets": dict(width=1920, height=1080, cameras=4, boxes=8, box_dist="pets")}
+SCALES = (1.0, 0.5)
+PERIOD = 4  # distinct frames per camera, played forth and back
+
+
+def ping_pong(t, period):
+    t %= 2 * period - 2
+    return t if t < period else 2 * period - 2 - t
+
+
+def child_run(a):
+    from mcmtt_opticalflow_amd import _lib, hip, synth
+    from mcmtt_opticalflow_amd import tracker2d as t2d
+
+    cfg, s = RUNS[a.run], a.scale
+    W, H, C, B = cfg["width"], cfg["height"], cfg["cameras"], cfg["boxes"]
+    hip.set_device(0)
+    scenes = [synth.make_scene(c, W, H, 512, nboxes=B, box_dist=cfg["box_dist"]) for c in range(C)]
+    d_frames = [[hip.DeviceBuffer.from_array(synth.to_bgr(sc.frame(t))) for t in range(PERIOD)] for sc in scenes]
+
+    def dets(t):
+        f = ping_pong(t, PERIOD)
+        out = []
+        for sc in scenes:
+            pts = sc.points_at(f) * np.float32(s)
+            cam = []
+            for k, (x, y) in enumerate(sc.box_at(f)):
+                b = (float(int(x)), float(int(y)), float(sc.box_ws[k]), float(sc.box_hs[k]))
+                head = (b[0] + b[2] / 4, b[1], b[2] / 2, b[3] / 8)
+                cam.append(t2d.make_detection(b, pts[sc.pt_box == k], head=head,
+                                              location=((b[0] + b[2] / 2) * 10.0, (b[1] + b[3]) * 10.0, 0.0),
+                                              height=1700.0))
+            out.append(cam)
+        return out
+
+    group = t2d.Group(W, H, list(range(C)), max_objects=2 * B, scale=None if s == 1.0 else s)
+
+    def push(t):
+        for c in range(C):
+            group.push_frame_device(c, d_frames[c][ping_pong(t, PERIOD)].addr, 3 * W, 3)
+
+    measure = 20
+    total = a.warmup + a.steps + measure
+    seq = [group.records(dets(t)) for t in range(total + 1)]
+
+    def step(t):
+        group.launch(t, seq[t])
+        push(t + 2)
+        group.complete_next(t + 1, seq[t + 1], raw=True)
+
+    push(0)
+    push(1)
+    for t in range(a.warmup):
+        step(t)
+    hip.synchronize()
+    t0 = time.perf_counter()
+    for t in range(a.warmup, a.warmup + a.steps):
+        step(t)
+    hip.synchronize()
+    elapsed = time.perf_counter() - t0
+    objects = sum(group.result_struct(c).num_objects for c in range(C))
+    L, lkh = _lib.load(), group.lk_handle()
+    L.psn_lk_enable_timing(lkh, 8 * measure + 64, 1)
+    for t in range(a.warmup + a.steps, total):
+        step(t)
+    hip.synchronize()
+    per = {}
+    for ms, tag in _lib.timing_launches(L, lkh, 8 * measure + 64):
+        k = _lib.kernel_of_tag(tag)
+        n, tot = per.get(k, (0, 0.0))
+        per[k] = (n + 1, tot + ms)
+    n_push, n_track = ctypes.c_int(), ctypes.c_int()
+    push_ms, track_ms = ctypes.c_double(), ctypes.c_double()
+    L.psn_lk_timing_stats(lkh, ctypes.byref(n_push), ctypes.byref(push_ms), ctypes.byref(n_track), ctypes.byref(track_ms))
+    group.close()
+    sizes = sorted({(int(w), int(h)) for sc in scenes for w, h in zip(sc.box_ws, sc.box_hs)})
+    print(json.dumps({
+        "run": a.run, "scale": s, "frame": f"{W}x{H}", "cameras": C, "boxes_per_camera": B,
+        "box_sizes": sizes if len(sizes) <= 4 else [sizes[0], "...", sizes[-1]],
+        "steps": a.steps, "warmup": a.warmup,
+        "camera_frames_per_s": round(C * a.steps / elapsed, 2), "frame_sets_per_s": round(a.steps / elapsed, 2),
+        "objects_last_frame": int(objects),
+        "lk_launches": {k: {"n": n, "mean_us": round(1e3 * tot / n, 1)} for k, (n, tot) in sorted(per.items())},
+        "push": {"n": n_push.value, "mean_us": round(1e3 * push_ms.value / max(n_push.value, 1), 1),
+                 "what": "pyramid build" + ("" if s == 1.0 else " + resize") + " per pushed frame (HIP events)"}}))
+
+
+def child_resize(a):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import oracle
+    import resize_ref
+    from mcmtt_opticalflow_amd import hip, lk, synth
+
+    W, H, s = a.width, a.height, a.scale
+    hip.set_device(0)
+    rt = hip.rt()
+    rt.hipEventCreate.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
+    rt.hipEventRecord.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    rt.hipEventSynchronize.argtypes = [ctypes.c_void_p]
+    rt.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]
+    ev = [ctypes.c_void_p(), ctypes.c_void_p()]
+    for e in ev:
+        hip.check(rt.hipEventCreate(ctypes.byref(e)), "hipEventCreate")
+    out = {"frame": f"{W}x{H}", "scale": s}
+    bgr = synth.to_bgr(synth.make_scene(0, W, H, 64).frame(0))
+    for ch, frame in ((3, bgr), (1, np.ascontiguousarray(bgr[..., 1]))):
+        d = hip.DeviceBuffer.from_array(frame)
+        with lk.LKContext(W, H, ring_slots=2, max_level_cap=3, scale=s) as ctx:
+            stream = ctx._L.psn_lk_get_stream(ctx.handle)
+            ctx.push_frame_device(0, d.addr, W * ch, ch)
+            gray = oracle.bgr2gray(frame) if ch == 3 else frame
+            assert np.array_equal(ctx.read_level(0, 0), resize_ref.resize(gray, s))  # results first
+            ctx.set_ingest_overlap(lk._lib.OVERLAP_FUSED)
+
+            def bracket(fn):
+                hip.check(rt.hipEventRecord(ev[0], stream), "record")
+                fn()
+                hip.check(rt.hipEventRecord(ev[1], stream), "record")
+                hip.check(rt.hipEventSynchronize(ev[1]), "sync")
+                t = ctypes.c_float()
+                hip.check(rt.hipEventElapsedTime(ctypes.byref(t), ev[0], ev[1]), "elapsed")
+                return 1e3 * t.value
+
+            ts, empty = [], []
+            for i in range(a.reps + 10):
+                t = bracket(lambda: ctx.push_frame_device(i & 1, d.addr, W * ch, ch))  # the resize only
+                ctx.sync()  # the deferred pyramid build, outside the events
+                e = bracket(lambda: None)
+                if i >= 10:
+                    ts.append(t)
+                    empty.append(e)
+            lw, lh = ctx.lk_width, ctx.lk_height
+        d.free()
+        ts.sort()
+        nbytes = W * H * ch + lw * lh
+        mean = sum(ts) / len(ts)
+        out["bgr" if ch == 3 else "gray"] = {
+            "lk_size": f"{lw}x{lh}", "bytes_read_plus_written": nbytes, "reps": len(ts),
+            "mean_us": round(mean, 2), "median_us": round(ts[len(ts) // 2], 2), "min_us": round(ts[0], 2),
+            "empty_event_pair_mean_us": round(sum(empty) / len(empty), 2),
+            "GBps_at_mean": round(nbytes / (mean * 1e-6) / 1e9, 1),
+            "GBps_at_median": round(nbytes / (ts[len(ts) // 2] * 1e-6) / 1e9, 1), "plane_checked": True}
+    print(json.dumps(out))
+
+
+def spawn(argv, timeout):
+    p = subprocess.run([sys.executable, os.path.abspath(__file__)] + argv, capture_output=True, text=True,
+                       timeout=timeout)
+    if p.returncode != 0:
+        raise RuntimeError(f"{argv}: exit {p.returncode}\n{p.stderr[-2000:]}")
+    return json.loads(p.stdout.strip().splitlines()[-1])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scale_time.json"))
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=100)
+    ap.add_argument("--child", choices=["run", "resize"], default=None)
+    ap.add_argument("--run", choices=sorted(RUNS), default="4k")
+    ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--width", type=int, default=3840)
+    ap.add_argument("--height", type=int, default=2160)
+    a = ap.parse_args()
+    if a.child == "run":
+        return child_run(a)
+    if a.child == "resize":
+        return child_resize(a)
+    res = {"runs": [], "resize": []}
+    common = ["--steps", str(a.steps), "--warmup", str(a.warmup), "--reps", str(a.reps)]
+    for name in ("4k", "pets"):
+        for s in SCALES:  # a failed child ends the tool: nothing more is started on the device
+            res["runs"].append(spawn(["--child", "run", "--run", name, "--scale", str(s)] + common, 420))
+            print(json.dumps(res["runs"][-1]), flush=True)
+    for W, H in ((3840, 2160), (1920, 1080)):
+        res["resize"].append(spawn(["--child", "resize", "--width", str(W), "--height", str(H), "--scale", "0.5"]
+                                   + common, 240))
+        print(json.dumps(res["resize"][-1]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
