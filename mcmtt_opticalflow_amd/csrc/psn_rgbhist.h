@@ -1,6 +1,6 @@
 // RGB box histograms of Associator3D's appearance feature (kernel in
 // psn_rgbhist.hip; the C ABI, psn_rgbhist_device / psn_lk_box_histograms of
-// include/psn_lk.h, in psn_lk_abi.cpp).
+// include/psn_lk.h, in psn_lk_readers.cpp).
 //
 // GetRGBFeature (psn_where/PSNWhere_Associator3D.cpp:2542-2556) over
 // psn::histogram (psn_where/PSNWhere_Utils.cpp:445-460): 16 bins of 16 grey
