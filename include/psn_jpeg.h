@@ -10,11 +10,18 @@
  * jpeg_idct_islow (jidctint.c), fancy triangle upsampling (jdsample.c),
  * fixed-point YCbCr->RGB (jdcolor.c), stored in OpenCV's BGR order.
  *
- * Device work per frame: one thread per restart interval decodes the entropy
- * data into coefficient blocks (a stream without restart markers is one
- * interval, decoded by one thread), one thread per 8x8 block runs the IDCT,
- * one thread per pixel pair upsamples the chroma, converts colour and writes
- * BGR. Results are bit-identical to libjpeg-turbo's decoder (the one PIL links)
+ * Device work per frame: the entropy data is decoded into coefficient blocks,
+ * one thread per 8x8 block runs the IDCT, one thread per pixel pair upsamples
+ * the chroma, converts colour and writes BGR. The entropy decode has two paths:
+ *   serial segments  one thread per restart interval (files with restart
+ *                    markers, and streams with fill bytes or embedded markers);
+ *   parallel         a stream without restart markers -- what cameras, encoders
+ *                    and PIL write by default -- is cut into fixed-size
+ *                    subsequences, one thread each: every subsequence is decoded
+ *                    from a cold state, exit states are handed to the successor
+ *                    until none changes (Huffman streams synchronise themselves),
+ *                    then a prefix sum places the blocks and a last pass writes
+ *                    them. Its output is the serial path's, byte for byte. Results are bit-identical to libjpeg-turbo's decoder (the one PIL links)
  * -- see oracle/jpeg_oracle.c for the pinning and for where OpenCV 2.4.6's
  * bundled libjpeg 8 differs (subsampled chroma).
  *
@@ -47,6 +54,62 @@ int psn_jpeg_set_stream(psn_jpeg_ctx *ctx, void *hip_stream);
 int psn_jpeg_decode_device(psn_jpeg_ctx *ctx, const uint8_t *data, size_t len, uint8_t *d_bgr, int stride);
 /* The same into host memory (synchronous). */
 int psn_jpeg_decode(psn_jpeg_ctx *ctx, const uint8_t *data, size_t len, uint8_t *bgr, int stride);
+
+/* ---- entropy paths ------------------------------------------------------- */
+
+#define PSN_JPEG_PATH_SERIAL 0   /* one thread per restart segment */
+#define PSN_JPEG_PATH_PARALLEL 1 /* self-synchronising subsequences */
+
+/* What the planner chooses for a file (host only, no device work). A stream is
+ * `plain` when every 0xFF of its entropy bytes is followed by 0x00 and the last
+ * byte is not 0xFF (no fill bytes, no embedded marker); the parallel path takes
+ * plain streams without restart intervals. */
+typedef struct psn_jpeg_plan {
+    int path;          /* PSN_JPEG_PATH_* */
+    int segments;      /* restart segments (1 without restart intervals) */
+    int plain;
+    int entropy_bytes;
+    int sub_bytes;     /* subsequence size (parallel path; else 0) */
+    int subsequences;  /* ceil(entropy_bytes / sub_bytes) */
+    int sequences;     /* groups of 256 subsequences, one workgroup each */
+} psn_jpeg_plan;
+int psn_jpeg_entropy_plan(const uint8_t *data, size_t len, psn_jpeg_plan *out);
+
+/* What the last decode of a context ran. The round counters are written by the
+ * kernels; sync_rounds is the largest round count of jpeg_sync_kernel over its
+ * workgroups (at most 256), chain_rounds the rounds of jpeg_chain_kernel (at
+ * most `sequences`), blocks the coefficient blocks of the scan that were
+ * decoded. */
+typedef struct psn_jpeg_stats {
+    int path;
+    int segments;
+    int sub_bytes;
+    int subsequences;
+    int sequences;
+    int sync_rounds;
+    int chain_rounds;
+    int blocks;
+} psn_jpeg_stats;
+/* Waits for the decoder's stream (the only call here that synchronises to read
+ * the counters). */
+int psn_jpeg_last_stats(psn_jpeg_ctx *ctx, psn_jpeg_stats *out);
+
+/* Diagnostics, like psn_lk_debug_set_variant: product contexts run the planner.
+ * mode 0: planner; 1: always the serial path; 2: the parallel path wherever it
+ * is legal. sub_bytes 0: the default (PSN_JPEG_DEFAULT_SUB_BYTES), otherwise a
+ * multiple of 4 in [4, 1024]. */
+#define PSN_JPEG_DEFAULT_SUB_BYTES 64 /* measured 64 / 128 / 256 at 1080p: DESIGN section 4 */
+int psn_jpeg_debug_set_entropy(psn_jpeg_ctx *ctx, int mode, int sub_bytes);
+
+/* CPU model of the entropy decode (host only): the symbol step the kernels run
+ * (csrc/psn_jpeg_entropy.h) with the kernels' rounds emulated sequentially.
+ * coef receives the scan's [blocks][64] coefficients in natural order, DC
+ * prediction applied -- what the device hands to its IDCT. mode and sub_bytes
+ * as above; mode 1 is the plain serial decode. Plain streams without restart
+ * intervals only (PSN_LK_ERR_UNSUPPORTED otherwise). With coef NULL nothing is
+ * decoded and stats->blocks is the scan's block count (the size of coef). */
+int psn_jpeg_entropy_model(const uint8_t *data, size_t len, int mode, int sub_bytes, int16_t *coef,
+                           psn_jpeg_stats *stats);
 
 #ifdef __cplusplus
 }

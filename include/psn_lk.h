@@ -185,6 +185,12 @@ int psn_lk_push_frame_async(psn_lk_ctx *ctx, int slot, const uint8_t *host, int 
  * the ingest stream; `jpeg` is copied before the call returns. */
 int psn_lk_push_frame_jpeg(psn_lk_ctx *ctx, int slot, const uint8_t *jpeg, size_t len);
 
+/* Which entropy path the context's last psn_lk_push_frame_jpeg took and its
+ * round counters (psn_jpeg_last_stats of the context's decoder; waits for the
+ * ingest stream). PSN_LK_ERR_ARG before the first JPEG push. */
+struct psn_jpeg_stats;
+int psn_lk_jpeg_last_stats(psn_lk_ctx *ctx, struct psn_jpeg_stats *out);
+
 /* Ingest overlap modes (default OFF: builds run on the context stream).
  * STREAM: psn_lk_push_frame* builds the pyramid on the context's internal
  *   ingest stream, ordered only against earlier LK launches that read the same

@@ -97,6 +97,25 @@ class RgbHistRect(ctypes.Structure):  # psn_rgbhist_rect
     ]
 
 
+class JpegPlan(ctypes.Structure):
+    """psn_jpeg_plan (include/psn_jpeg.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("path", "segments", "plain", "entropy_bytes", "sub_bytes",
+                                            "subsequences", "sequences")]
+
+
+class JpegStats(ctypes.Structure):
+    """psn_jpeg_stats (include/psn_jpeg.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("path", "segments", "sub_bytes", "subsequences", "sequences",
+                                            "sync_rounds", "chain_rounds", "blocks")]
+
+
+JPEG_PATH_SERIAL, JPEG_PATH_PARALLEL = 0, 1
+
+
+def struct_dict(s: ctypes.Structure) -> dict:
+    return {n: getattr(s, n) for n, _ in s._fields_}
+
+
 def header_functions() -> list[str]:
     """Names of every function declared in include/psn_lk.h and psn_sgsmooth.h."""
     src = "".join(open(p).read() for p in HEADER_PATHS)
@@ -203,6 +222,12 @@ def load(path: str | None = None):
     L.psn_jpeg_set_stream.argtypes = [vp, vp]
     L.psn_jpeg_decode_device.argtypes = [vp, vp, ctypes.c_size_t, vp, ip]
     L.psn_jpeg_decode.argtypes = [vp, vp, ctypes.c_size_t, vp, ip]
+    if hasattr(L, "psn_jpeg_entropy_plan"):  # (absent from the A/B experiments' older builds only)
+        L.psn_jpeg_entropy_plan.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(JpegPlan)]
+        L.psn_jpeg_debug_set_entropy.argtypes = [vp, ip, ip]
+        L.psn_jpeg_last_stats.argtypes = [vp, ctypes.POINTER(JpegStats)]
+        L.psn_jpeg_entropy_model.argtypes = [vp, ctypes.c_size_t, ip, ip, vp, ctypes.POINTER(JpegStats)]
+        L.psn_lk_jpeg_last_stats.argtypes = [vp, ctypes.POINTER(JpegStats)]
     L.psn_lk_debug_set_variant.argtypes = [vp, ip, ip]
     L.psn_lk_track.argtypes = [vp, ctypes.POINTER(LkQuery), ip, fp, fp, u8p, fp]
     L.psn_lk_track_device.argtypes = [vp, ctypes.POINTER(LkQuery), ip, vp, vp, vp, vp]

@@ -8,6 +8,22 @@
 //   K1     jpeg_entropy_kernel: one thread per restart segment decodes its MCUs
 //          (jdhuff.c: fill with 0xFF00 unstuffing, a marker feeds zeros; DC
 //          prediction reset per segment) into int16 coefficient blocks
+//   K1p    a plain stream without restart intervals takes four kernels in K1's
+//          place (the symbol step they share with the CPU model is
+//          psn_jpeg_entropy.h):
+//          jpeg_sync_kernel   one thread per subsequence of S bytes, 256 to a
+//                             workgroup: decode from a cold state, then take the
+//                             predecessor's exit state and decode again until no
+//                             exit state of the workgroup changes
+//          jpeg_chain_kernel  one workgroup, one thread per 256-subsequence
+//                             sequence: carry the exit states across sequences to
+//                             the fixed point, then the exclusive prefix sum of
+//                             the blocks completed per subsequence
+//          jpeg_emit_kernel   one thread per subsequence decodes from its true
+//                             entry state and writes coefficients (DC: the
+//                             difference)
+//          jpeg_dc_kernel     one workgroup per component: inclusive scan of the
+//                             DC differences in scan order
 //   K2     jpeg_idct_kernel: one thread per 8x8 block, dequantise + islow IDCT
 //          (jidctint.c, 64-bit intermediates as libjpeg-turbo's JLONG) + the
 //          post-IDCT range-limit table -> component planes (u8)
@@ -26,19 +42,13 @@
 #include <vector>
 
 #include "psn_jpeg.h"
+#include "psn_jpeg_entropy.h"  // HuffDev, the symbol step of the parallel path
 #include "psn_lk.h"
 
 namespace psn {
 namespace {
 
 constexpr int kJpegMaxComp = 3;
-
-struct HuffDev {            // one Huffman table (jdhuff.c d_derived_tbl)
-    int maxcode[18];        // largest code of length l, -1 if none; [17] sentinel
-    int valoff[18];         // vals index = code + valoff[l]
-    uint16_t fast[512];     // 9-bit lookahead: (len << 8) | value, 0 = longer code
-    uint8_t vals[256];
-};
 
 struct Tables {             // device copy per frame
     uint16_t qt[4][64];     // natural order
@@ -174,6 +184,258 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(JpegArgs A) {
                     }
                 }
         }
+    }
+}
+
+// ---------------------------------------------------------------- parallel path
+// Subsequence i owns the bits [i * 8S, (i + 1) * 8S) of the entropy bytes: its
+// thread decodes the symbols that start there, and its exit state is the state at
+// the first symbol boundary at or past its end.
+
+struct DevStats {           // written by the kernels, read by psn_jpeg_last_stats
+    int sync_rounds, chain_rounds, blocks, pad;
+};
+
+struct EntArgs {
+    const Tables *tab;
+    const uint8_t *data;     // entropy bytes (readable 16 bytes past len)
+    long long len;
+    int S;                   // subsequence bytes
+    int nsub, nseq;          // subsequences, sequences of jent::kSeqLen
+    int stage;               // 1: the workgroup's bytes are staged in LDS
+    int nb0, bpm, nmcu;
+    int td[kJpegMaxComp], ta[kJpegMaxComp];
+    jent::Geo geo;
+    unsigned long long *st;  // [nsub] exit state
+    unsigned *cnt;           // [nsub] blocks completed inside the subsequence
+    unsigned *pre;           // [nsub] exclusive prefix sum of cnt
+    int *seq_rounds;         // [nseq] rounds of jpeg_sync_kernel's workgroup
+    DevStats *stats;
+    int16_t *coef;
+};
+
+struct LdsTabs {            // the scan's tables by component (lookups are divergent)
+    HuffDev dc[kJpegMaxComp], ac[kJpegMaxComp];
+};
+static_assert(sizeof(LdsTabs) % 16 == 0, "LDS carve offsets stay 16-byte aligned");
+constexpr int kNaturalLds = 96;  // jpeg_emit_kernel's LDS copy of the natural-order table (80 bytes, carve stays 16-aligned)
+constexpr int kStageSlack = 64;  // bytes staged past the workgroup's last subsequence (a symbol may span its end)
+
+__device__ __forceinline__ void stage_tables(const EntArgs &E, LdsTabs &L) {
+    constexpr int nd = (int)(sizeof(HuffDev) / 4);
+    for (int c = 0; c < E.geo.nc; c++) {
+        const uint32_t *sd = (const uint32_t *)&E.tab->dc[E.td[c]], *sa = (const uint32_t *)&E.tab->ac[E.ta[c]];
+        uint32_t *dd = (uint32_t *)&L.dc[c], *da = (uint32_t *)&L.ac[c];
+        for (int k = threadIdx.x; k < nd; k += blockDim.x) {
+            dd[k] = sd[k];
+            da[k] = sa[k];
+        }
+    }
+}
+
+// Bytes by index: the staged window [w0, w1) from LDS, the rest from global
+// memory, zeros from len on.
+struct DevBytes {
+    const uint8_t *lds;
+    long long w0, w1;
+    const uint8_t *g;
+    long long len;
+    __device__ __forceinline__ unsigned operator()(long long i) const {
+        if (i >= w0 && i < w1) return lds[i - w0];
+        return i < len ? g[i] : 0u;
+    }
+};
+
+// Stage the bytes of the workgroup's kSeqLen subsequences (plus slack) as dwords.
+__device__ __forceinline__ DevBytes stage_bytes(const EntArgs &E, uint8_t *sb) {
+    DevBytes src{sb, 0, 0, E.data, E.len};
+    if (E.stage) {
+        src.w0 = (long long)blockIdx.x * jent::kSeqLen * E.S;
+        src.w1 = min(src.w0 + (long long)jent::kSeqLen * E.S + kStageSlack, E.len);
+        const int nd = (int)((src.w1 - src.w0 + 3) / 4);  // the last dword may read past len: inside the blob's slack
+        const uint32_t *s = (const uint32_t *)(E.data + src.w0);
+        for (int k = threadIdx.x; k < nd; k += blockDim.x) ((uint32_t *)sb)[k] = s[k];
+    }
+    return src;
+}
+
+__global__ __launch_bounds__(256) void jpeg_sync_kernel(EntArgs E) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    LdsTabs &L = *(LdsTabs *)smem;
+    unsigned long long *sx = (unsigned long long *)(smem + sizeof(LdsTabs));  // exit state per thread
+    stage_tables(E, L);
+    const DevBytes src = stage_bytes(E, smem + sizeof(LdsTabs) + jent::kSeqLen * 8);
+    __syncthreads();
+    const jent::Tabs T{L.dc, L.ac, E.nb0, E.bpm};
+    const int t = threadIdx.x;
+    const long long i = (long long)blockIdx.x * jent::kSeqLen + t;
+    const bool active = i < E.nsub;
+    const long long subbits = 8LL * E.S;
+    const unsigned long long end = (unsigned long long)((i + 1) * subbits);
+    unsigned long long entry = 0, ex = 0;
+    unsigned cnt = 0;
+    if (active) {  // round 0: from cold (the stream's first thread from the true state)
+        entry = i ? jent::cold_state(src, i * E.S) : jent::pack(0, 0, 0);
+        jent::CountSink cs;
+        ex = jent::run(src, T, entry, end, subbits + 1, cs);
+        cnt = cs.blocks;
+    }
+    sx[t] = ex;
+    int rounds = 1;
+    __syncthreads();
+    for (int r = 1; r < jent::kSeqLen; r++) {  // thread r is final after round r
+        const unsigned long long pred = t ? sx[t - 1] : entry;
+        __syncthreads();
+        int changed = 0;
+        if (active && t && pred != entry) {
+            entry = pred;
+            jent::CountSink cs;
+            const unsigned long long e = jent::run(src, T, entry, end, subbits + 1, cs);
+            cnt = cs.blocks;
+            if (e != ex) {
+                ex = e;
+                sx[t] = e;
+                changed = 1;
+            }
+        }
+        rounds++;
+        if (!__syncthreads_or(changed)) break;
+    }
+    if (active) {
+        E.st[i] = ex;
+        E.cnt[i] = cnt;
+    }
+    if (t == 0) E.seq_rounds[blockIdx.x] = rounds;
+}
+
+// Inclusive scan over the workgroup (any multiple of 64 threads up to 1024);
+// `ws` holds one word per wave. Every thread calls it.
+__device__ __forceinline__ unsigned block_scan_incl(unsigned v, unsigned *ws, unsigned *total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned u = __shfl_up(v, d, 64);
+        if (lane >= d) v += u;
+    }
+    __syncthreads();  // the previous call's reads of ws are done
+    if (lane == 63) ws[w] = v;
+    __syncthreads();
+    unsigned off = 0, tot = 0;
+    for (int k = 0; k < nw; k++) {
+        const unsigned x = ws[k];
+        if (k < w) off += x;
+        tot += x;
+    }
+    *total = tot;
+    return v + off;
+}
+
+__global__ __launch_bounds__(1024) void jpeg_chain_kernel(EntArgs E) {
+    __shared__ LdsTabs L;
+    __shared__ unsigned long long sx[jent::kChainLen];  // last exit state of each sequence of the pass
+    __shared__ unsigned ws[16];
+    __shared__ int smax;
+    const int tid = threadIdx.x;
+    stage_tables(E, L);
+    if (tid == 0) smax = 0;
+    __syncthreads();
+    const jent::Tabs T{L.dc, L.ac, E.nb0, E.bpm};
+    const DevBytes src{nullptr, 0, 0, E.data, E.len};
+    const long long subbits = 8LL * E.S;
+    int rounds = 0;
+    unsigned long long carry = jent::pack(0, 0, 0);  // the state entering the pass's first sequence
+    for (int c0 = 0; c0 < E.nseq; c0 += jent::kChainLen) {
+        const int j = c0 + tid, npass = min(jent::kChainLen, E.nseq - c0);
+        const bool active = j < E.nseq;
+        const long long first = (long long)j * jent::kSeqLen, last = min(first + jent::kSeqLen, (long long)E.nsub) - 1;
+        if (active) sx[tid] = E.st[last];
+        unsigned long long walked = ~0ULL;  // the entry state the sequence's stored states follow from
+        __syncthreads();
+        for (int r = 0; r < npass; r++) {  // the pass's sequence r is final after round r
+            const unsigned long long entry = tid ? sx[active ? tid - 1 : 0] : carry;
+            __syncthreads();
+            int changed = 0;
+            if (active && j > 0 && entry != walked) {
+                // sequence 0 was decoded from the true state; every other one from a cold
+                // state: walk it from its entry until the walk meets the stored states
+                unsigned long long cur = entry;
+                bool met = false;
+                for (long long i = first; i <= last && !met; i++) {
+                    jent::CountSink cs;
+                    cur = jent::run(src, T, cur, (unsigned long long)((i + 1) * subbits), subbits + 1, cs);
+                    met = cur == E.st[i];
+                    E.st[i] = cur;
+                    E.cnt[i] = cs.blocks;
+                }
+                if (!met && cur != sx[tid]) {
+                    sx[tid] = cur;
+                    changed = 1;
+                }
+                walked = entry;
+            }
+            rounds++;
+            if (!__syncthreads_or(changed)) break;
+        }
+        __syncthreads();
+        carry = sx[npass - 1];
+        __syncthreads();
+    }
+    // exclusive prefix sum of the blocks per subsequence
+    unsigned run_sum = 0;
+    for (long long base = 0; base < E.nsub; base += blockDim.x) {
+        const long long i = base + tid;
+        const unsigned v = i < E.nsub ? E.cnt[i] : 0u;
+        unsigned tot;
+        const unsigned incl = block_scan_incl(v, ws, &tot);
+        if (i < E.nsub) E.pre[i] = run_sum + incl - v;
+        run_sum += tot;
+    }
+    int m = 0;
+    for (int k = tid; k < E.nseq; k += blockDim.x) m = max(m, E.seq_rounds[k]);
+    atomicMax(&smax, m);
+    __syncthreads();
+    if (tid == 0) {
+        E.stats->sync_rounds = smax;
+        E.stats->chain_rounds = rounds;
+    }
+}
+
+__global__ __launch_bounds__(256) void jpeg_emit_kernel(EntArgs E) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    LdsTabs &L = *(LdsTabs *)smem;
+    uint8_t *snat = smem + sizeof(LdsTabs);  // the natural-order table: a divergent lookup per coefficient
+    stage_tables(E, L);
+    if (threadIdx.x < 64 + 16) snat[threadIdx.x] = jent::kNaturalDev[threadIdx.x];
+    const DevBytes src = stage_bytes(E, smem + sizeof(LdsTabs) + kNaturalLds);
+    __syncthreads();
+    const long long i = (long long)blockIdx.x * jent::kSeqLen + threadIdx.x;
+    if (i >= E.nsub) return;
+    const jent::Tabs T{L.dc, L.ac, E.nb0, E.bpm};
+    const long long subbits = 8LL * E.S, total = E.geo.total;
+    const bool last = i == E.nsub - 1;
+    const long long g0 = E.pre[i];
+    jent::EmitSink sink(E.geo, T, E.coef, snat, g0);
+    // the last thread goes on past its end, and past the data (zeros), to the scan's
+    // last block, as the serial reader does for a truncated file: at most 64 symbols a block
+    const unsigned long long end = last ? ~0ULL >> 16 : (unsigned long long)((i + 1) * subbits);
+    const long long bound = subbits + 1 + (last ? (total - min(g0, total) + 1) * 64 : 0);
+    jent::run(src, T, i ? E.st[i - 1] : jent::pack(0, 0, 0), end, bound, sink);
+    if (last) E.stats->blocks = (int)min(sink.g, total);
+}
+
+__global__ __launch_bounds__(1024) void jpeg_dc_kernel(EntArgs E) {
+    __shared__ unsigned ws[16];
+    const int ci = blockIdx.x;
+    const long long n = (long long)E.nmcu * E.geo.c[ci].h * E.geo.c[ci].v;
+    unsigned last_dc = 0;  // the serial kernel's last_dc[ci], modulo 2^32
+    for (long long base = 0; base < n; base += blockDim.x) {
+        const long long e = base + threadIdx.x;
+        long long blk = e < n ? jent::dc_block(E.geo, ci, e) : -1;
+        if (blk >= E.geo.nblocks) blk = -1;
+        const unsigned v = blk >= 0 ? (unsigned)(int)E.coef[blk * 64] : 0u;
+        unsigned tot;
+        const unsigned incl = block_scan_incl(v, ws, &tot);
+        if (blk >= 0) E.coef[blk * 64] = (int16_t)(int)(last_dc + incl);
+        last_dc += tot;
     }
 }
 
@@ -341,6 +603,11 @@ struct psn_jpeg_ctx {
     bool blob_pending = false;
     uint8_t *d_out = nullptr;  // psn_jpeg_decode's device BGR buffer
     size_t out_cap = 0;
+    int ent_mode = 0, ent_sub = 0;  // psn_jpeg_debug_set_entropy
+    uint8_t *d_par = nullptr;       // parallel path: [DevStats | states | counts | prefix sums | rounds]
+    size_t par_cap = 0;
+    psn_jpeg_stats last{};          // the last decode (host part; the kernels' counters are in d_par)
+    bool decoded = false;
     std::string err;
 };
 
@@ -369,6 +636,9 @@ struct Parsed {
     psn::JpegArgs a{};
     std::vector<int> seg;
     size_t ent0 = 0, ent1 = 0;  // entropy bytes [ent0, ent1) of the file
+    // every 0xFF in [ent0, ent1) is followed by 0x00 and the last byte is not 0xFF:
+    // no fill bytes, no embedded marker (psn_jpeg_entropy.h reads such streams)
+    bool plain = true;
     // per Huffman slot (class tc, index th): 0 never defined, 1 valid, -1 the last
     // definition is one jpeg_make_d_derived_tbl rejects -- an error only for a table
     // the scan uses (libjpeg builds the derived tables of the scan's components)
@@ -487,20 +757,183 @@ int parse(const uint8_t *d, size_t n, Parsed &P, std::string &why) {
             const int mk = d[q + 1];
             if (mk >= 0xD0 && mk <= 0xD7) {
                 if (a.ri) P.seg.push_back((int)(q + 2 - P.ent0));
+                P.plain = false;  // a marker inside the entropy bytes
                 q += 2;
                 continue;
             }
             break;  // EOI or another marker ends the scan
         }
+        if (d[q] == 0xFF && d[q + 1] == 0xFF) P.plain = false;  // a fill byte
         q++;
     }
     P.ent1 = q;
+    if (P.ent1 > P.ent0 && d[P.ent1 - 1] == 0xFF) P.plain = false;
     const int want = a.ri ? (a.nmcu + a.ri - 1) / a.ri : 1;
     if ((int)P.seg.size() < want) return why = "missing restart markers", PSN_LK_ERR_ARG;
     P.seg.resize((size_t)want);
     a.nseg = want;
     a.data_len = (int)(P.ent1 - P.ent0);
     return PSN_LK_OK;
+}
+
+namespace jent = psn::jent;
+
+// Bytes of a workgroup's subsequences are staged in LDS up to this subsequence
+// size (256 subsequences + tables + states stay under 64 KiB); larger ones are
+// read from global memory.
+#ifndef PSN_JPEG_STAGE_MAX_SUB
+#define PSN_JPEG_STAGE_MAX_SUB 128
+#endif
+
+bool valid_entropy_request(int mode, int sub) {
+    return mode >= 0 && mode <= 2 && (sub == 0 || (sub >= jent::kMinSub && sub <= jent::kMaxSub && sub % 4 == 0));
+}
+
+// The planner: the parallel path is legal for a plain stream without restart
+// intervals, and it is the planner's choice wherever it is legal.
+void plan_entropy(const Parsed &P, int mode, int sub, psn_jpeg_plan &pl) {
+    memset(&pl, 0, sizeof pl);
+    pl.segments = P.a.nseg;
+    pl.plain = P.plain ? 1 : 0;
+    pl.entropy_bytes = P.a.data_len;
+    const bool legal = P.a.ri == 0 && P.plain && P.a.data_len > 0;
+    pl.path = mode != 1 && legal ? PSN_JPEG_PATH_PARALLEL : PSN_JPEG_PATH_SERIAL;
+    if (pl.path == PSN_JPEG_PATH_PARALLEL) {
+        pl.sub_bytes = sub ? sub : PSN_JPEG_DEFAULT_SUB_BYTES;
+        pl.subsequences = (P.a.data_len + pl.sub_bytes - 1) / pl.sub_bytes;
+        pl.sequences = (pl.subsequences + jent::kSeqLen - 1) / jent::kSeqLen;
+    }
+}
+
+// The scan's block layout as the symbol step's sinks address it.
+void entropy_geometry(const Parsed &P, jent::Geo &G, int &nb0, int &bpm) {
+    const psn::JpegArgs &a = P.a;
+    memset(&G, 0, sizeof G);
+    G.nc = a.nc;
+    G.mcux = a.mcux;
+    G.nblocks = a.nblocks;
+    for (int c = 0; c < a.nc; c++) {
+        G.c[c].h = a.nc == 1 ? 1 : a.c[c].h;
+        G.c[c].v = a.nc == 1 ? 1 : a.c[c].v;
+        G.c[c].bw = a.c[c].bw;
+        G.c[c].blk0 = a.c[c].blk0;
+    }
+    nb0 = G.c[0].h * G.c[0].v;
+    bpm = a.nc == 1 ? 1 : nb0 + a.nc - 1;  // chroma is 1x1 (parse())
+    G.total = a.nmcu * bpm;
+}
+
+// psn_jpeg_entropy_model's decode: the kernels' passes, one after the other.
+void model_decode(const Parsed &P, const uint8_t *ent, const psn_jpeg_plan &pl, int16_t *coef, psn_jpeg_stats &S) {
+    jent::Geo G;
+    int nb0, bpm;
+    entropy_geometry(P, G, nb0, bpm);
+    std::vector<psn::HuffDev> dc(psn::kJpegMaxComp), ac(psn::kJpegMaxComp);
+    for (int c = 0; c < P.a.nc; c++) {
+        dc[c] = P.tab.dc[P.a.c[c].td];
+        ac[c] = P.tab.ac[P.a.c[c].ta];
+    }
+    const jent::Tabs T{dc.data(), ac.data(), nb0, bpm};
+    const jent::HostBytes src{ent, P.a.data_len};
+    const long long total = G.total;
+    const unsigned long long kNoEnd = ~0ULL >> 16, kStart = jent::pack(0, 0, 0);
+    memset(coef, 0, (size_t)G.nblocks * 64 * sizeof(int16_t));
+    if (pl.path == PSN_JPEG_PATH_SERIAL) {
+        jent::EmitSink sink(G, T, coef, jent::kNaturalHost, 0);
+        jent::run(src, T, kStart, kNoEnd, (total + 1) * 64, sink);
+        S.blocks = (int)std::min(sink.g, total);
+    } else {
+        const int nsub = pl.subsequences, nseq = pl.sequences, K = jent::kSeqLen;
+        const long long subbits = 8LL * pl.sub_bytes;
+        std::vector<unsigned long long> st((size_t)nsub);
+        std::vector<unsigned> cnt((size_t)nsub);
+        auto sub = [&](long long i, unsigned long long from, unsigned &blocks) {
+            jent::CountSink cs;
+            const unsigned long long e = jent::run(src, T, from, (unsigned long long)((i + 1) * subbits), subbits + 1, cs);
+            blocks = cs.blocks;
+            return e;
+        };
+        // jpeg_sync_kernel: every thread of a round sees the previous round's exit states
+        for (int q = 0; q < nseq; q++) {
+            const long long i0 = (long long)q * K;
+            const int n = (int)std::min<long long>(K, nsub - i0);
+            std::vector<unsigned long long> entry((size_t)n), ex((size_t)n);
+            for (int t = 0; t < n; t++) {
+                entry[t] = i0 + t ? jent::cold_state(src, (i0 + t) * pl.sub_bytes) : kStart;
+                ex[t] = sub(i0 + t, entry[t], cnt[i0 + t]);
+            }
+            int rounds = 1;
+            for (int r = 1; r < K; r++) {
+                const std::vector<unsigned long long> prev = ex;
+                bool changed = false;
+                for (int t = 1; t < n; t++)
+                    if (prev[t - 1] != entry[t]) {
+                        entry[t] = prev[t - 1];
+                        const unsigned long long e = sub(i0 + t, entry[t], cnt[i0 + t]);
+                        changed |= e != ex[t];
+                        ex[t] = e;
+                    }
+                rounds++;
+                if (!changed) break;
+            }
+            std::copy(ex.begin(), ex.end(), st.begin() + i0);
+            S.sync_rounds = std::max(S.sync_rounds, rounds);
+        }
+        // jpeg_chain_kernel
+        unsigned long long carry = kStart;
+        for (int c0 = 0; c0 < nseq; c0 += jent::kChainLen) {
+            const int npass = std::min(jent::kChainLen, nseq - c0);
+            std::vector<unsigned long long> sx((size_t)npass), walked((size_t)npass, ~0ULL);
+            auto last_of = [&](int j) { return std::min<long long>((long long)(j + 1) * K, nsub) - 1; };
+            for (int t = 0; t < npass; t++) sx[t] = st[last_of(c0 + t)];
+            for (int r = 0; r < npass; r++) {
+                const std::vector<unsigned long long> prev = sx;
+                bool changed = false;
+                for (int t = 0; t < npass; t++) {
+                    const int j = c0 + t;
+                    const unsigned long long entry = t ? prev[t - 1] : carry;
+                    if (j == 0 || entry == walked[t]) continue;
+                    unsigned long long cur = entry;
+                    bool met = false;
+                    for (long long i = (long long)j * K; i <= last_of(j) && !met; i++) {
+                        unsigned blocks;
+                        cur = sub(i, cur, blocks);
+                        met = cur == st[i];
+                        st[i] = cur;
+                        cnt[i] = blocks;
+                    }
+                    if (!met && cur != sx[t]) {
+                        sx[t] = cur;
+                        changed = true;
+                    }
+                    walked[t] = entry;
+                }
+                S.chain_rounds++;
+                if (!changed) break;
+            }
+            carry = sx[npass - 1];
+        }
+        // prefix sum, jpeg_emit_kernel
+        long long g0 = 0;
+        for (long long i = 0; i < nsub; i++) {
+            const bool last = i == nsub - 1;
+            jent::EmitSink sink(G, T, coef, jent::kNaturalHost, g0);
+            const long long bound = subbits + 1 + (last ? (total - std::min(g0, total) + 1) * 64 : 0);
+            jent::run(src, T, i ? st[i - 1] : kStart, last ? kNoEnd : (unsigned long long)((i + 1) * subbits), bound, sink);
+            if (last) S.blocks = (int)std::min(sink.g, total);
+            g0 += cnt[i];
+        }
+    }
+    // jpeg_dc_kernel: the serial kernel's last_dc[ci] += diff; blk[0] = (int16_t)last_dc[ci]
+    for (int c = 0; c < P.a.nc; c++) {
+        const long long n = (long long)P.a.nmcu * G.c[c].h * G.c[c].v;
+        unsigned last_dc = 0;
+        for (long long e = 0; e < n; e++) {
+            int16_t &d0 = coef[jent::dc_block(G, c, e) * 64];
+            last_dc += (unsigned)(int)d0;
+            d0 = (int16_t)(int)last_dc;
+        }
+    }
 }
 
 }  // namespace
@@ -539,7 +972,7 @@ void psn_jpeg_destroy(psn_jpeg_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (void *p : {(void *)c->d_blob, (void *)c->d_coef, (void *)c->d_planes, (void *)c->d_out})
+    for (void *p : {(void *)c->d_blob, (void *)c->d_coef, (void *)c->d_planes, (void *)c->d_out, (void *)c->d_par})
         if (p) (void)hipFree(p);
     if (c->h_blob) (void)hipHostFree(c->h_blob);
     if (c->blob_free) (void)hipEventDestroy(c->blob_free);
@@ -615,8 +1048,58 @@ int psn_jpeg_decode_device(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uin
     a.planes = c->d_planes;
     a.out = d_bgr;
     a.out_stride = stride;
-    hipLaunchKernelGGL(psn::jpeg_entropy_kernel, dim3((a.nseg + 63) / 64), dim3(64), 0, c->stream, a);
-    JCHK(c, hipGetLastError());
+    psn_jpeg_plan pl;
+    plan_entropy(P, c->ent_mode, c->ent_sub, pl);
+    c->last = psn_jpeg_stats{pl.path, pl.segments, pl.sub_bytes, pl.subsequences, pl.sequences, 0, 0, 0};
+    c->decoded = true;
+    if (pl.path == PSN_JPEG_PATH_PARALLEL) {
+        const size_t nsub = (size_t)pl.subsequences, nseq = (size_t)pl.sequences;
+        auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+        const size_t off_st = up16(sizeof(psn::DevStats)), off_cnt = off_st + up16(8 * nsub), off_pre = off_cnt + up16(4 * nsub),
+                     off_rounds = off_pre + up16(4 * nsub), par = off_rounds + up16(4 * nseq);
+        if (c->par_cap < par) {
+            JCHK(c, hipStreamSynchronize(c->stream));
+            if (c->d_par) (void)hipFree(c->d_par);
+            c->d_par = nullptr;
+            c->par_cap = 0;
+            JCHK(c, hipMalloc(&c->d_par, par + par / 2));
+            c->par_cap = par + par / 2;
+        }
+        psn::EntArgs e{};
+        e.tab = a.tab;
+        e.data = a.data;
+        e.len = a.data_len;
+        e.S = pl.sub_bytes;
+        e.nsub = pl.subsequences;
+        e.nseq = pl.sequences;
+        e.stage = pl.sub_bytes <= PSN_JPEG_STAGE_MAX_SUB ? 1 : 0;
+        entropy_geometry(P, e.geo, e.nb0, e.bpm);
+        e.nmcu = a.nmcu;
+        for (int i = 0; i < a.nc; i++) {
+            e.td[i] = a.c[i].td;
+            e.ta[i] = a.c[i].ta;
+        }
+        e.stats = (psn::DevStats *)c->d_par;
+        e.st = (unsigned long long *)(c->d_par + off_st);
+        e.cnt = (unsigned *)(c->d_par + off_cnt);
+        e.pre = (unsigned *)(c->d_par + off_pre);
+        e.seq_rounds = (int *)(c->d_par + off_rounds);
+        e.coef = a.coef;
+        const size_t staged = e.stage ? (size_t)jent::kSeqLen * e.S + psn::kStageSlack : 0;
+        const size_t lds_sync = sizeof(psn::LdsTabs) + jent::kSeqLen * 8 + staged, lds_emit = sizeof(psn::LdsTabs) + psn::kNaturalLds + staged;
+        hipLaunchKernelGGL(psn::jpeg_sync_kernel, dim3(e.nseq), dim3(jent::kSeqLen), lds_sync, c->stream, e);
+        JCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(psn::jpeg_chain_kernel, dim3(1), dim3(1024), 0, c->stream, e);
+        JCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(psn::jpeg_emit_kernel, dim3(e.nseq), dim3(jent::kSeqLen), lds_emit, c->stream, e);
+        JCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(psn::jpeg_dc_kernel, dim3(a.nc), dim3(1024), 0, c->stream, e);
+        JCHK(c, hipGetLastError());
+    } else {
+        c->last.blocks = a.nblocks;  // the serial kernel decodes every block of the scan
+        hipLaunchKernelGGL(psn::jpeg_entropy_kernel, dim3((a.nseg + 63) / 64), dim3(64), 0, c->stream, a);
+        JCHK(c, hipGetLastError());
+    }
     hipLaunchKernelGGL(psn::jpeg_idct_kernel, dim3((a.nblocks + 255) / 256), dim3(256), 0, c->stream, a);
     JCHK(c, hipGetLastError());
     hipLaunchKernelGGL(psn::jpeg_color_kernel, dim3((a.W + 255) / 256, a.H), dim3(256), 0, c->stream, a);
@@ -644,6 +1127,57 @@ int psn_jpeg_decode(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uint8_t *b
     if (rc) return rc;
     JCHK(c, hipMemcpy2DAsync(bgr, stride, c->d_out, 3 * (size_t)w, 3 * (size_t)w, h, hipMemcpyDeviceToHost, c->stream));
     JCHK(c, hipStreamSynchronize(c->stream));
+    return PSN_LK_OK;
+}
+
+int psn_jpeg_entropy_plan(const uint8_t *data, size_t len, psn_jpeg_plan *out) {
+    if (!data || !out) return PSN_LK_ERR_ARG;
+    Parsed P;
+    std::string why;
+    const int rc = parse(data, len, P, why);
+    if (rc) return rc;
+    plan_entropy(P, 0, 0, *out);
+    return PSN_LK_OK;
+}
+
+int psn_jpeg_debug_set_entropy(psn_jpeg_ctx *c, int mode, int sub_bytes) {
+    if (!c) return PSN_LK_ERR_ARG;
+    if (!valid_entropy_request(mode, sub_bytes))
+        return jerr(c, PSN_LK_ERR_ARG, "entropy mode %d (0..2), sub_bytes %d (0 or a multiple of 4 in [4, 1024])", mode, sub_bytes);
+    c->ent_mode = mode;
+    c->ent_sub = sub_bytes;
+    return PSN_LK_OK;
+}
+
+int psn_jpeg_last_stats(psn_jpeg_ctx *c, psn_jpeg_stats *out) {
+    if (!c || !out) return PSN_LK_ERR_ARG;
+    if (!c->decoded) return jerr(c, PSN_LK_ERR_ARG, "nothing decoded yet");
+    JCHK(c, hipSetDevice(c->device));
+    JCHK(c, hipStreamSynchronize(c->stream));
+    *out = c->last;
+    if (c->last.path == PSN_JPEG_PATH_PARALLEL) {
+        psn::DevStats d;
+        JCHK(c, hipMemcpy(&d, c->d_par, sizeof d, hipMemcpyDeviceToHost));
+        out->sync_rounds = d.sync_rounds;
+        out->chain_rounds = d.chain_rounds;
+        out->blocks = d.blocks;
+    }
+    return PSN_LK_OK;
+}
+
+int psn_jpeg_entropy_model(const uint8_t *data, size_t len, int mode, int sub_bytes, int16_t *coef, psn_jpeg_stats *stats) {
+    if (!data || !stats || !valid_entropy_request(mode, sub_bytes)) return PSN_LK_ERR_ARG;
+    Parsed P;
+    std::string why;
+    const int rc = parse(data, len, P, why);
+    if (rc) return rc;
+    if (P.a.ri != 0 || !P.plain) return PSN_LK_ERR_UNSUPPORTED;
+    psn_jpeg_plan pl;
+    plan_entropy(P, mode, sub_bytes, pl);
+    *stats = psn_jpeg_stats{pl.path, pl.segments, pl.sub_bytes, pl.subsequences, pl.sequences, 0, 0, P.a.nblocks};
+    if (!coef) return PSN_LK_OK;
+    stats->blocks = 0;
+    model_decode(P, data + P.ent0, pl, coef, *stats);
     return PSN_LK_OK;
 }
 

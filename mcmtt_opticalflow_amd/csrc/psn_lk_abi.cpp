@@ -658,6 +658,14 @@ int psn_lk_push_frame_jpeg(psn_lk_ctx *c, int slot, const uint8_t *jpeg, size_t 
     return ingest_build(c, slot, c->d_stage[slot], (int)row, 3, c->ingest_stream);
 }
 
+int psn_lk_jpeg_last_stats(psn_lk_ctx *c, struct psn_jpeg_stats *out) {
+    if (!c || !out) return PSN_LK_ERR_ARG;
+    if (!c->jpeg) return set_err(c, PSN_LK_ERR_ARG, "no JPEG frame pushed yet");
+    const int rc = psn_jpeg_last_stats(c->jpeg, out);
+    if (rc) return set_err(c, rc, "JPEG stats: %s", psn_jpeg_last_error(c->jpeg));
+    return PSN_LK_OK;
+}
+
 int psn_lk_push_frame_async(psn_lk_ctx *c, int slot, const uint8_t *host, int stride, int channels) {
     if (!c || !host || (channels != 1 && channels != 3) || stride < c->src_w * channels) return PSN_LK_ERR_ARG;
     if (check_user_slot(c, slot)) return PSN_LK_ERR_SLOT;

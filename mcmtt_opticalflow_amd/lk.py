@@ -178,6 +178,12 @@ class LKContext:
         buf = ctypes.create_string_buffer(bytes(data), len(data))
         self._check(self._L.psn_lk_push_frame_jpeg(self._h, slot, buf, len(data)), "push_frame_jpeg")
 
+    def jpeg_stats(self) -> dict:
+        """psn_lk_jpeg_last_stats: the entropy path of the last push_frame_jpeg and its round counters."""
+        s = _lib.JpegStats()
+        self._check(self._L.psn_lk_jpeg_last_stats(self._h, ctypes.byref(s)), "jpeg_stats")
+        return _lib.struct_dict(s)
+
     def push_frame_device(self, slot: int, dev_ptr: int, stride: int, channels: int = 1):
         self._check(self._L.psn_lk_push_frame_device(self._h, slot, dev_ptr, stride, channels), "push_frame_device")
 
@@ -407,13 +413,52 @@ class SGSmoother:
 class JpegDecoder:
     """psn_jpeg (include/psn_jpeg.h): baseline JPEG -> BGR on the device."""
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, entropy: int = 0, sub_bytes: int = 0):
+        """entropy / sub_bytes: psn_jpeg_debug_set_entropy (0, 0: the planner and the
+        default subsequence size, what product contexts run)."""
         self._L = _lib.load()
         h = ctypes.c_void_p()
         rc = self._L.psn_jpeg_create(device, ctypes.byref(h))
         if rc != 0:
             raise PsnLkError(rc, "psn_jpeg_create")
         self._h = h
+        if entropy or sub_bytes:
+            rc = self._L.psn_jpeg_debug_set_entropy(self._h, entropy, sub_bytes)
+            if rc != 0:
+                msg = self._L.psn_jpeg_last_error(self._h).decode()
+                self.close()
+                raise PsnLkError(rc, f"psn_jpeg_debug_set_entropy: {msg}")
+
+    def stats(self) -> dict:
+        """psn_jpeg_last_stats: the path the last decode took and its round counters."""
+        s = _lib.JpegStats()
+        rc = self._L.psn_jpeg_last_stats(self._h, ctypes.byref(s))
+        if rc != 0:
+            raise PsnLkError(rc, f"psn_jpeg_last_stats: {self._L.psn_jpeg_last_error(self._h).decode()}")
+        return _lib.struct_dict(s)
+
+    @staticmethod
+    def plan(data: bytes) -> dict:
+        """psn_jpeg_entropy_plan: the planner's choice for a file (host only)."""
+        p = _lib.JpegPlan()
+        rc = _lib.load().psn_jpeg_entropy_plan(data, len(data), ctypes.byref(p))
+        if rc != 0:
+            raise PsnLkError(rc, "psn_jpeg_entropy_plan")
+        return _lib.struct_dict(p)
+
+    @staticmethod
+    def model(data: bytes, entropy: int = 0, sub_bytes: int = 0):
+        """psn_jpeg_entropy_model (host only): ((blocks, 64) int16 coefficients, stats)."""
+        L = _lib.load()
+        s = _lib.JpegStats()
+        rc = L.psn_jpeg_entropy_model(data, len(data), entropy, sub_bytes, None, ctypes.byref(s))
+        if rc != 0:
+            raise PsnLkError(rc, "psn_jpeg_entropy_model")
+        coef = np.empty((s.blocks, 64), np.int16)
+        rc = L.psn_jpeg_entropy_model(data, len(data), entropy, sub_bytes, coef.ctypes.data, ctypes.byref(s))
+        if rc != 0:
+            raise PsnLkError(rc, "psn_jpeg_entropy_model")
+        return coef, _lib.struct_dict(s)
 
     def close(self):
         if getattr(self, "_h", None):
