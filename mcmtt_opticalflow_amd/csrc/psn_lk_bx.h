@@ -1,7 +1,9 @@
-// Device helpers of the box-window LK kernel (lk_kernel_bx, psn_lk_kernels.hip)
+// Device helpers of the box-window LK kernel (lk_kernel_bx, psn_lk_bx.hip)
 // shared with the large-window kernel (lk_kernel_lg, psn_lk_large.hip): packed
-// 16-bit dot products, the per-chain exactness records (publish / check / eval),
-// the ordered LDS chain sums, the XCD-aware workgroup order. Internal.
+// 16-bit dot products (also the single-tile kernel's, psn_lk_st.hip), the
+// per-chain exactness records (publish / check / eval), the ordered LDS chain
+// sums, the fallbacks' plane stores, the XCD-aware workgroup order (also
+// pyramid_kernel's, psn_lk_kernels.hip). Internal.
 #pragma once
 
 #include "psn_lk_device.h"
@@ -253,6 +255,34 @@ __device__ __forceinline__ void bx_diffs(const uint32_t *jp, int JRP4, unsigned 
                                          unsigned s1, unsigned s2, unsigned s3, const unsigned (&ip)[2], int (&d)[4],
                                          int c256) {
     bx_diffs2(jp, jp + JRP4, W0, W1, s0, s1, s2, s3, ip, d, c256);
+}
+// The fallbacks' plane stores of one unit whose four pixels are all inside the
+// window and feed the SSE2 lane chains: pixel i goes to lane region i (stride S)
+// at the unit's slot d1, one plane (pitch P) per sum. The callers keep their
+// register pins. Called by the own-units paths; the half-wave and quarter-wave
+// tile writers repeat these lines (through the helpers their builds gain a
+// VGPR or run 0.5 % slower), and the dummy-slot forms (unitA, tile_unit) differ.
+// A fallback: Ix*Ix, Ix*Iy, Iy*Iy of the packed gradient pairs xp, yp.
+__device__ __forceinline__ void bx_store_a(float *d1, const unsigned (&xp)[2], const unsigned (&yp)[2], int S, int P) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int gx = (i & 1) ? hi16(xp[i >> 1]) : lo16(xp[i >> 1]);
+        const int gy = (i & 1) ? hi16(yp[i >> 1]) : lo16(yp[i >> 1]);
+        d1[i * S] = (float)__mul24(gx, gx);
+        d1[i * S + P] = (float)__mul24(gx, gy);
+        d1[i * S + 2 * P] = (float)__mul24(gy, gy);
+    }
+}
+// b fallback: (J - I)*Ix, (J - I)*Iy of the unit's diffs d.
+__device__ __forceinline__ void bx_store_b(float *d1, const int (&d)[4], const unsigned (&xp)[2], const unsigned (&yp)[2],
+                                           int S, int P) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int gx = (i & 1) ? hi16(xp[i >> 1]) : lo16(xp[i >> 1]);
+        const int gy = (i & 1) ? hi16(yp[i >> 1]) : lo16(yp[i >> 1]);
+        d1[i * S] = (float)__mul24(d[i], gx);
+        d1[i * S + P] = (float)__mul24(d[i], gy);
+    }
 }
 // pair selector: bytes (sj + i, sj + i + 1) of a row's 8-byte window -> J[x] | J[x+1] << 16
 __device__ __forceinline__ unsigned bx_sel(int sj, int i) {

@@ -1,5 +1,5 @@
 // Device helpers shared by the LK kernels of libpsn_lk.so (psn_lk_kernels.hip,
-// psn_lk_large.hip): OpenCV 2.4.6 rounding / border rules, workgroup sums, the
+// psn_lk_st.hip, psn_lk_bx.hip, psn_lk_large.hip): OpenCV 2.4.6 rounding / border rules, workgroup sums, the
 // LDS staging walkers and the SSE2 chain layouts. Internal, not installed.
 //
 // The scalar steps of LKTrackerInvoker itself -- the structure-tensor solve and

@@ -451,18 +451,19 @@ static_assert(kBxMaxLds <= kMaxLdsBytes && kBxLdsTarget <= kBxMaxLds && 2 * kBxM
 constexpr int kStEPTMax = 4;  // window pixels per thread held in registers by the single-tile kernel
 constexpr int kStMaxLds = 150 * 1024;
 
-// Launchers (psn_lk_kernels.hip).
+// Launchers, one translation unit per kernel family.
+// Pyramid build and tiled kernel (psn_lk_kernels.hip).
 hipError_t launch_pyramid(const PyrBuildArgs &a, hipStream_t s);
 void pyramid_grid(const PyrBuildArgs &a, int &tiles_x, int &tiles_y, int &lds_bytes);
 // Tiled kernel with a workgroup of `threads` (64, 128 or 256).
 hipError_t launch_lk(const LkLaunchArgs &a, int total_wgs, int threads, int lds_bytes, hipStream_t s);
-// Single-tile kernel lk_kernel_st<nt, ept, e, occ>: workgroup size, window pixels
-// per thread, window rows per lane of the one-wave iteration mode (0: multi-wave
-// iterations), workgroups per CU the build is held to (1 or 3). A combination
-// that is not instantiated (PSN_ST_KERNELS, psn_lk_kernels.hip) is hipErrorInvalidValue.
+// Single-tile kernel (psn_lk_st.hip) lk_kernel_st<nt, ept, e, occ>: workgroup size,
+// window pixels per thread, window rows per lane of the one-wave iteration mode
+// (0: multi-wave iterations), workgroups per CU the build is held to (1 or 3). A
+// combination that is not instantiated (PSN_ST_KERNELS) is hipErrorInvalidValue.
 hipError_t launch_lk_st(const LkLaunchArgs &a, int total_wgs, int nt, int ept, int e, int occ, int lds_bytes,
                         hipStream_t s);
-// Box-window kernel with UPT units per thread (4, 8, 10, 12 or 16).
+// Box-window kernel (psn_lk_bx.hip, PSN_BX_KERNELS) with UPT units per thread (4, 8, 10, 12 or 16).
 // notail: every query of the launch sums in the SSE2 order with width % 8 == 0
 // (no scalar-tail chain: a build without its per-pixel bookkeeping); nt: the
 // workgroup size (kBxNT, or kBxNT2 for the two-wave build <8, true>)
@@ -470,7 +471,11 @@ hipError_t launch_lk_bx(const LkLaunchArgs &a, int total_wgs, int upt, bool nota
                         hipStream_t s);
 // Large-window kernel (psn_lk_large.hip): `grid` workgroups over a.lk_wgs points.
 hipError_t launch_lk_lg(const LkLaunchArgs &a, int grid, int lds_bytes, int tq, hipStream_t s);
+// Each family's unit raises the dynamic-LDS limit of its own kernels;
+// lk_kernels_init (psn_lk_kernels.hip) does so for its own and calls the others.
+hipError_t st_kernels_init();
+hipError_t bx_kernels_init();
 hipError_t lg_kernels_init();
-hipError_t lk_kernels_init();   // raises the dynamic-LDS limit once
+hipError_t lk_kernels_init();
 
 }  // namespace psn

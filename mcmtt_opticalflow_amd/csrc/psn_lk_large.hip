@@ -4,7 +4,7 @@
 // size (forward w x h, backward w x w; PETS-scale 100x250 at 1080p, 128x320 at
 // 4K).
 //
-// The structure of lk_kernel_bx (psn_lk_kernels.hip) with the window values
+// The structure of lk_kernel_bx (psn_lk_bx.hip) with the window values
 // streamed instead of register-resident. One workgroup (4 waves) per point, the
 // grid striding over the launch's points. The window is cut into quads (row y,
 // 4 pixels) in row-major order; thread t owns the CONTIGUOUS quads [t*K, t*K+K),

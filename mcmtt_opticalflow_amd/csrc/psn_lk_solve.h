@@ -1,8 +1,8 @@
 // The per-point solver arithmetic of LKTrackerInvoker (OpenCV 2.4.6), once.
 //
 // This header is the ONE place that restates the invoker's scalar float steps;
-// every LK kernel (lk_kernel, lk_kernel_st, lk_kernel_bx in psn_lk_kernels.hip,
-// lk_kernel_lg in psn_lk_large.hip) calls it and differs only in how the sums
+// every LK kernel (lk_kernel in psn_lk_kernels.hip, lk_kernel_st in psn_lk_st.hip,
+// lk_kernel_bx in psn_lk_bx.hip, lk_kernel_lg in psn_lk_large.hip) calls it and differs only in how the sums
 // are produced and where the window lives. The bit-exactness of every GPU test
 // against the oracle rests on these lines; oracle/lk_oracle.c pins them
 // (minEig at :725, the D test at :729).

@@ -15,7 +15,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
-KERNELS = os.path.join(ROOT, "mcmtt_opticalflow_amd", "csrc", "psn_lk_kernels.hip")
+KERNELS = os.path.join(ROOT, "mcmtt_opticalflow_amd", "csrc", "psn_lk_bx.hip")
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC) and not shutil.which("hipcc"), reason="hipcc absent")
 

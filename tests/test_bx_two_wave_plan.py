@@ -5,6 +5,7 @@ workgroups per CU that LDS and registers allow -- six, against four of the
 objects (tools/kernel_resources.py)."""
 import json
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -126,6 +127,40 @@ def test_built_kernel_registers():
         r = [r for n, r in ks.items() if f"ILi{upt}ELb1ELi256E" in n]
         assert len(r) == 1, sorted(ks)
         assert int(r[0]["vgpr"]) == vgpr and int(r[0]["vgpr_spill"]) == 0 and int(r[0]["scratch"]) == 0, (upt, r)
+
+
+def test_instantiation_lists_match_built_kernels():
+    """Each family's instantiation list, in the unit that owns the family, against the
+    built library's code objects: exactly 17 lk_kernel_st and 11 lk_kernel_bx kernels,
+    and every list entry among them (a variant cannot launch without its instantiation,
+    also with the lists in separate files)."""
+    assert os.path.exists(LIB), "build() first: " + LIB
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import kernel_resources
+    finally:
+        sys.path.pop(0)
+    csrc = os.path.join(ROOT, "mcmtt_opticalflow_amd", "csrc")
+    hdr = open(os.path.join(csrc, "psn_lk_kernels.h")).read()
+    const = {k: int(v) for k, v in re.findall(r"\b(kBx(?:NT2?|UPT2)) = (\d+)[,;]", hdr)}
+
+    def entries(unit, macro):
+        src = open(os.path.join(csrc, unit)).read()
+        body = re.search(r"#define " + macro + r"\(X\)((?:.*\\\n)*.*)\n", src).group(1)
+        return [[a.strip() for a in e.split(",")] for e in re.findall(r"X\(([^)]*)\)", body)]
+
+    def num(a):
+        return const[a] if a in const else int(a)
+
+    st = ["lk_kernel_stILi%dELi%dELi%dELi%dE" % tuple(num(a) for a in e) for e in entries("psn_lk_st.hip", "PSN_ST_KERNELS")]
+    bx = ["lk_kernel_bxILi%dELb%dELi%dE" % (num(u), nt == "true", num(n)) for u, nt, n in entries("psn_lk_bx.hip", "PSN_BX_KERNELS")]
+    assert len(st) == len(set(st)) == 17 and len(bx) == len(set(bx)) == 11, (st, bx)
+    built = list(kernel_resources.kernels(LIB))
+    for family, want in (("lk_kernel_st", st), ("lk_kernel_bx", bx)):
+        have = [n for n in built if family + "I" in n]
+        assert len(have) == len(want), (family, sorted(have))
+        for key in want:
+            assert sum(key in n for n in have) == 1, (key, sorted(have))
 
 
 def test_box_kernel_names_agree():

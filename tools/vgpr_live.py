@@ -6,8 +6,10 @@ architectural VGPRs and prints the points of highest pressure with the source
 lines (.loc, build with -gline-tables-only) where the live registers were last
 defined -- which values the allocator has to hold at the peak.
 
-  hipcc ... --cuda-device-only -S -gline-tables-only -o k.s psn_lk_kernels.hip
-  python tools/vgpr_live.py k.s _ZN3psn12lk_kernel_bxILi10EEEvNS_12LkLaunchArgsE
+  hipcc ... --cuda-device-only -S -gline-tables-only -o k.s psn_lk_bx.hip
+  python tools/vgpr_live.py k.s _ZN3psn12lk_kernel_bxILi10ELb1ELi256EEEvNS_12LkLaunchArgsE
+(the kernel's unit: psn_lk_bx.hip, psn_lk_st.hip, psn_lk_kernels.hip or psn_lk_large.hip;
+the csrc Makefile's `asm` target writes the plain listing of each)
 """
 import re
 import sys
