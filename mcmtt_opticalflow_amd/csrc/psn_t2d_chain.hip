@@ -4,7 +4,7 @@
 // workgroup of 128 lanes per detection (<= 100 points, one point per lane).
 //
 // LocalSearchKLT, step by step (the host version is
-// mcmtt_opticalflow_amd/host/tracker2d_flow.cpp):
+// mcmtt_opticalflow_amd/host/tracker2d_steps.cpp):
 //   1. d_i = nextPts_i - prevPts_i in float, widened to double; a vector
 //      "moves" unless |d_i| < 0.1 * scale (:477-490);
 //   2. fewer than half moving -> the box stays, no inliers (:493-496);

@@ -16,42 +16,15 @@
 
 #include <cstdint>
 #include <list>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "psn_lk.h"
-#include "psn_types.hpp"
+#include "tracker2d_device.hpp"
+#include "tracker2d_steps.hpp"
 
 namespace psn {
-
-constexpr int kT2dInterval = 4;          // PSN_2D_BACKTRACKING_INTERVAL (:16)
-// the ring + two staging slots: frame t+2 uploads (and its pyramid builds) while
-// frame t+1 waits staged and frame t runs
-constexpr int kT2dStaging = 2;
-constexpr int kSlotsPerCam = kT2dInterval + kT2dStaging;
-constexpr size_t kT2dMinFeatures = 4;    // PSN_2D_FEATURE_MIN_NUM_TRACK (:12)
-constexpr size_t kT2dMaxFeatures = 100;  // PSN_2D_FEATURE_MAX_NUM_TRACK (:13)
-constexpr int kT2dResBlocks = 3;         // chain result blocks used in turn by consecutive passes
-// PSN_2D_OPTICALFLOW_SCALE (:18) is a runtime value here: Tracker2DFlow's scale,
-// the `scale` argument of LocalSearchKLT (a product with a runtime 1.0 is exact,
-// so one code path serves both of the reference's builds)
-constexpr double kWinSizeRatio = 1.0;    // PSN_2D_FEATURE_WIN_SIZE_RATIO (:15)
-
-// preBox is the box already scaled; scale enters the minimum movement (:481) and,
-// a second time, the neighbour window (:502), as in the reference
-Rect LocalSearchKLT(Rect preBox, const std::vector<Point2f> &preFeatures, const std::vector<Point2f> &curFeatures,
-                    std::vector<size_t> &inlierFeatureIndex, double scale = 1.0);
-double BoxMatchingCost(const Rect &box1, const Rect &box2);
-void ResultWithTracker(const Tracker2D &tracker, Object2DInfo &out);
-// tracker2d_match.cpp: the assignment of Track2D_MatchingAndUpdating (inf
-// handling + minimum-cost matching, :1040-1064) and the update (:1066-1164)
-std::vector<int> AssignDetections(const std::vector<float> &cost, size_t rows, size_t cols);
-// CPSNWhere_Hungarian::Match (helpers/PSNWhere_Hungarian.cpp:212-359): matched pairs in row-major order
-bool HungarianMatch(const std::vector<float> &cost, size_t rows, size_t cols, std::vector<int> &outRows,
-                    std::vector<int> &outCols, std::vector<float> &outCosts);
-void MatchingAndUpdating(std::vector<DetectedObject> &dets, std::deque<Tracker2D *> &active,
-                         std::list<Tracker2D> &storage, const std::vector<int> &match, unsigned frameIdx,
-                         unsigned &newTrackerID, Track2DResult &result);
 
 class Tracker2DFlow {
   public:
@@ -161,18 +134,6 @@ class Tracker2DFlow {
     const std::string &last_error() const { return err_; }
 
   private:
-    struct Job {  // one calcOpticalFlowPyrLK call
-        int prev_slot, next_slot, win_w, win_h;
-        const std::vector<Point2f> *in;
-        std::vector<Point2f> *out;
-        std::vector<uint8_t> *status;
-    };
-    struct Chain {  // one detection's backward chain (host-chain mode)
-        size_t obj;
-        std::vector<Point2f> curr, prev;
-        std::vector<uint8_t> status;
-        bool active;
-    };
     struct Cam {  // per-camera state
         unsigned camID = 0;
         int ring[kT2dInterval];  // slot ids, oldest first; ring[kT2dInterval - 1] = frame t
@@ -204,11 +165,21 @@ class Tracker2DFlow {
         size_t fwd_n = 0;   // forward outputs to copy back (that launch's index range)
         int fwd_par = 0;    // the forward output block its forward launch wrote
     };
-    int PassLaunch(std::vector<PassCam> &pc, bool gridfast, uint32_t seed);  // chains, then forward
-    int PassLaunchChains(std::vector<PassCam> &pc, bool gridfast, uint32_t seed);
-    int PassLaunchForward(std::vector<PassCam> &pc);
-    int LaunchForwardFromChains(std::vector<PassCam> &pc, int src_rb, bool host_fallback);
-    static int forward_window_error(int w, int h);
+
+    // ---- shared: the context, the cameras' rings and trackers, the last error ----
+    psn_lk_ctx *lk_ = nullptr;
+    std::vector<Cam> cams_;
+    int width_ = 0, height_ = 0;  // frame (source) size
+    int lk_w_ = 0, lk_h_ = 0;     // the LK context's size: the frame at scale_
+    double scale_ = 1.0;
+    std::vector<char> filled_;  // per LK slot
+    std::string err_;
+    bool device_chain_ = true;
+    int fail(int rc, const char *what);
+    int StepsAvailable(size_t cam) const;  // chain steps the camera's ring holds frames for (0..3)
+    bool StepAvailable(int step) const { return step <= StepsAvailable(0); }
+
+    // ---- the device pass (tracker2d_pass.cpp): streams, buffers, schedule ----
     // what a chain pass leaves for the next frame's forward launch
     struct ChainInfo {
         bool valid = false;
@@ -216,18 +187,51 @@ class Tracker2DFlow {
         std::vector<size_t> k0, ndet;                // per camera
         std::vector<std::pair<int, int>> win;        // per chain: the forward window of the detection's box
     };
-    ChainInfo chain_info_[kT2dResBlocks];
-    int next_rb_ = 0, last_rb_ = -1;
-    int trk_rb_ = -1;  // the result block holding the current trackers' set 0 (their next forward call)
-    void *ev_set0_[3] = {nullptr, nullptr, nullptr};   // hipEvent_t: a block's set 0 is final (chain stream)
-    void *ev_fread_[3] = {nullptr, nullptr, nullptr};  // hipEvent_t: the forward launch reading a block is done
-    // Forward outputs alternate between two device blocks, so that a frame's
-    // result copy (on its chain stream) never sits between two forward launches
-    // on the forward stream: ev_fend_[p] = forward launch into block p done,
-    // ev_fcopied_[p] = block p copied to the host (the next launch into p waits)
-    int fwd_par_ = 0;
-    void *ev_fend_[2] = {nullptr, nullptr}, *ev_fcopied_[2] = {nullptr, nullptr};
-    bool fread_rec_[3] = {false, false, false};
+    struct Cursor {  // where the next chain pass goes; saved and put back around a launch that may fail
+        int next_rb = 0, last_rb = -1;  // the result block to try first, the previous pass's
+        int stage = 0;                  // staging set of the next chain launch
+    };
+    struct Schedule {
+        Cursor cur;
+        int trk_rb = -1;  // the result block holding the current trackers' set 0 (their next forward call)
+        ChainInfo chain_info[kT2dResBlocks];
+        // per result block: its set 0 is final (chain stream); the forward launch reading it is done
+        Event set0[kT2dResBlocks], fread[kT2dResBlocks];
+        // Forward outputs alternate between two device blocks, so that a frame's
+        // result copy (on its chain stream) never sits between two forward launches
+        // on the forward stream: fend[p] = forward launch into block p done,
+        // fcopied[p] = block p copied to the host (the next launch into p waits)
+        int fwd_par = 0;
+        Event fend[2], fcopied[2];
+        Event gf;                    // after a pass's GridFAST launches (the context's detector scratch)
+        Event chain_done, fwd_done;  // a pass's result copies done: what PassSync polls
+    } sched_;
+    // forward launches (lowest priority) alternate between the two streams (output
+    // blocks 0 and 1): a frame's forward may start while the last one's slowest
+    // workgroups still run
+    Stream fwd_streams_[2];
+    // the backward chains (highest priority): pass i of the staging set si runs on
+    // chain_streams_[si], so the chains of frame t+1 start beside frame t's last steps
+    Stream chain_streams_[2];
+    hipStream_t FwdStream(int par) const { return fwd_streams_[par ? 1 : 0].get(); }
+    hipStream_t ChainStream(int si) const { return chain_streams_[si & 1].get(); }
+    hipStream_t LkStream() const { return static_cast<hipStream_t>(psn_lk_get_stream(lk_)); }
+    void SyncForward();
+    void SyncChains();
+    std::unique_ptr<DeviceBuffers> dev_;
+    std::vector<psn_lk_query> queries_, fwd_queries_;
+    // per chain of a pass (per staging set): window the LK cannot run (error only if the chain has points)
+    std::vector<char> win_bad_sets_[2];
+    void Chk(hipError_t e, const char *what, int &rc);  // the first HIP error of a sequence: err_ and rc
+    static psn_lk_query Query(int prev_slot, int next_slot, size_t first_pt, size_t num_pts);
+    static int WindowError(int w, int h);       // the error of a window the LK cannot run, or 0
+    void Roi(const Rect &box, int *roi) const;  // GridFAST's roi of a detection box
+    template <class Launch>
+    int OnForwardStream(int par, Launch launch, hipError_t &recorded);
+    int PassLaunch(std::vector<PassCam> &pc, bool gridfast, uint32_t seed);  // chains, then forward
+    int PassLaunchChains(std::vector<PassCam> &pc, bool gridfast, uint32_t seed);
+    int PassLaunchForward(std::vector<PassCam> &pc);
+    int LaunchForwardFromChains(std::vector<PassCam> &pc, int src_rb, bool host_fallback);
     int PassComplete(std::vector<PassCam> &pc, bool gridfast);  // PassWait + PassFeatures + PassUnpack
     int PassWait(std::vector<PassCam> &pc);  // PassCopy + PassSync
     int PassCopy(std::vector<PassCam> &pc);  // enqueue the result copies, record the completion events
@@ -235,57 +239,15 @@ class Tracker2DFlow {
     int PassFeatures(std::vector<PassCam> &pc, bool gridfast);
     void PassUnpack(std::vector<PassCam> &pc);
     bool ChainsFit(const std::vector<CamFrame> &io) const;
-
-    int RunJobs(std::vector<Job> &jobs);
-    int fail(int rc, const char *what);
-    void BackwardBegin(const std::vector<Detection> &dets, const std::vector<std::vector<Point2f>> &features,
-                       std::vector<DetectedObject> &out, std::vector<Chain> &chains);
-    void BackwardJobs(int step, std::vector<Chain> &chains, const std::vector<DetectedObject> &out,
-                      std::vector<Job> &jobs);
-    void BackwardStepDone(std::vector<Chain> &chains, std::vector<DetectedObject> &out);
-    void BackwardEnd(std::vector<DetectedObject> &out, const std::vector<std::vector<Point2f>> &features);
-    int StepsAvailable(size_t cam) const;  // chain steps the camera's ring holds frames for (0..3)
-    bool StepAvailable(int step) const { return step <= StepsAvailable(0); }
     int EnsureChains(size_t nchains);
     int EnsureForward(size_t nfwd_pts, size_t nfwd_jobs);
-    void ForwardJobs(size_t cam, const std::vector<Tracker2D *> &trackers, std::vector<std::vector<uint8_t>> &status,
-                     std::vector<Job> &jobs);
-    void ForwardDone(const std::vector<Tracker2D *> &trackers, std::vector<std::vector<uint8_t>> &status,
-                     const std::vector<DetectedObject> &dets, std::vector<float> &cost);
     int DevicePass(const std::vector<Detection> &dets, std::vector<std::vector<Point2f>> &features,
                    std::vector<DetectedObject> &out, std::vector<Job> *fwd, bool gridfast, uint32_t seed);
 
-    psn_lk_ctx *lk_ = nullptr;
-    void *fwd_stream_ = nullptr;    // hipStream_t of the forward launch, beside the chain's launches (lowest priority)
-    // consecutive forward launches alternate between fwd_stream_ (output block 0)
-    // and fwd_stream2_ (block 1): a frame's forward may start while the last
-    // one's slowest workgroups still run
-    void *fwd_stream2_ = nullptr;
-    void *FwdStream(int par) const { return par ? fwd_stream2_ : fwd_stream_; }
-    void SyncForward();
-    // the backward chains (highest priority): pass i of the staging set si runs on
-    // chain_streams_[si], so the chains of frame t+1 start beside frame t's last steps
-    void *ev_gf_ = nullptr;  // after a pass's GridFAST launches (the context's detector scratch)
-    bool gf_rec_ = false;
-    void *chain_streams_[2] = {nullptr, nullptr};
-    void *ChainStream(int si) const { return chain_streams_[si & 1]; }
-    void SyncChains();
-    std::vector<psn_lk_query> fwd_queries_;
-    std::vector<Cam> cams_;
-    int width_ = 0, height_ = 0;  // frame (source) size
-    int lk_w_ = 0, lk_h_ = 0;     // the LK context's size: the frame at scale_
-    double scale_ = 1.0;
-    std::vector<char> filled_;  // per LK slot
-    std::string err_;
-    // batched-call staging
-    std::vector<float> xy_in_, xy_out_, err_out_, gf_xy_;
+    // ---- the camera Run and the single-camera API (tracker2d_flow.cpp) ----
+    int RunJobs(std::vector<Job> &jobs);
+    std::vector<float> xy_in_, xy_out_, err_out_, gf_xy_;  // batched-call staging
     std::vector<uint8_t> st_out_;
-    std::vector<psn_lk_query> queries_;
-    // per chain of a pass (per staging set): window the LK cannot run (error only if the chain has points)
-    std::vector<char> win_bad_sets_[2];
-    int stage_ = 0;  // staging set of the next chain launch
-    void *ev_chain_ = nullptr, *ev_fwd_ = nullptr;  // hipEvent_t: a pass's result copies done
-    bool wait_chain_ = false, wait_fwd_ = false;
     int AdoptFrames(std::vector<CamFrame> &io, bool gridfast, std::vector<PassCam> &pass, unsigned frameIdx);
     std::vector<long long> slot_frame_;  // per LK slot: the frame index it was adopted as, or -1
     void UnadoptFrames();  // AdoptFrames undone: frame t's slot back to staging, the oldest back in the ring
@@ -297,9 +259,6 @@ class Tracker2DFlow {
     long host_calls_ = 0;
     unsigned run_frame_ = 0;
     bool run_gridfast_ = false;
-    bool device_chain_ = true;
-    struct DeviceBuffers;
-    DeviceBuffers *dev_ = nullptr;
 };
 
 }  // namespace psn

@@ -7,7 +7,7 @@
 #include <cmath>
 #include <limits>
 
-#include "tracker2d_flow.hpp"
+#include "tracker2d_steps.hpp"
 
 namespace psn {
 
