@@ -265,6 +265,11 @@ int psn_lk_timing_stats(psn_lk_ctx *ctx, int *n_push, double *push_ms, int *n_tr
  * launches (one per window class) gets 1000 + the tag of the launch with the
  * most window pixels. *n = the calls written (<= cap). */
 int psn_lk_timing_launches(psn_lk_ctx *ctx, int cap, double *ms, int *tag, int *n);
+/* The same calls' kernel entries: the tag above, but 10 * UPT + 3 where the
+ * box build ran on its forward entry, lk_kernel_fw<UPT, no-tail> (the same body
+ * and results as lk_kernel_bx<UPT, no-tail>, whose tag the call keeps above:
+ * the tag names the build, the entry what was launched). */
+int psn_lk_timing_entries(psn_lk_ctx *ctx, int cap, int *entry, int *n);
 
 /* Kernel-variant selection for tests and experiments (never read from the
  * environment: a product context always runs the planner's choice). Applies
@@ -289,6 +294,10 @@ int psn_lk_timing_launches(psn_lk_ctx *ctx, int cap, double *ms, int *tag, int *
  *   PSN_LK_VARIANT_BX_WAVES    0 = planner; 4 = never the two-wave build of lk_kernel_bx;
  *                              2 = the two-wave build (128 threads, 8 units per thread)
  *                              for every no-tail box window it fits
+ *   PSN_LK_VARIANT_FW          0 = planner; 1 = never the forward entry lk_kernel_fw;
+ *                              2 = the forward entry for every launch it fits (the
+ *                              no-tail build of 10 units per thread: windows of
+ *                              2,049 - 2,560 units of 4 px, Tracker2D's 64 x 160)
  * Queries are split into one launch per window class (single-tile / box kernel
  * per units-per-thread and tail build / row-tiled / large), each sized for its
  * own windows. */
@@ -304,6 +313,7 @@ int psn_lk_timing_launches(psn_lk_ctx *ctx, int cap, double *ms, int *tag, int *
 #define PSN_LK_VARIANT_ST_OVL 10
 #define PSN_LK_VARIANT_POISON_LDS 11
 #define PSN_LK_VARIANT_BX_WAVES 12
+#define PSN_LK_VARIANT_FW 13
 int psn_lk_debug_set_variant(psn_lk_ctx *ctx, int key, int value);
 
 /* Window-sample counter (SURVEY 8(d)'s compute figure): while on, every box-

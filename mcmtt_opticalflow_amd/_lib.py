@@ -40,7 +40,7 @@ MAX_WIN_WIDTH = 6400  # PSN_LK_MAX_WIN_WIDTH (any window height)
 COMM_UNIQUE_ID_BYTES = 128
 # psn_lk_debug_set_variant keys (tests / experiments; never read from the environment)
 VARIANTS = {"threads": 1, "generic": 2, "onewave": 3, "box": 4, "tiled_lds": 5, "fused_helpers": 6,
-            "large": 7, "lg_lds": 8, "lg_jr": 9, "st_ovl": 10, "poison_lds": 11, "bx_waves": 12}
+            "large": 7, "lg_lds": 8, "lg_jr": 9, "st_ovl": 10, "poison_lds": 11, "bx_waves": 12, "fw": 13}
 
 
 class PsnLkError(RuntimeError):
@@ -140,9 +140,26 @@ def timing_launches(L, ctx, cap: int):
     return [(ms[i], tag[i]) for i in range(n.value)]
 
 
+def timing_entries(L, ctx, cap: int):
+    """psn_lk_timing_entries -> the entry tag per timed LK call."""
+    entry = (ctypes.c_int * max(cap, 1))()
+    n = ctypes.c_int()
+    rc = L.psn_lk_timing_entries(ctx, cap, entry, ctypes.byref(n))
+    if rc != 0:
+        raise PsnLkError(rc, "psn_lk_timing_entries")
+    return [entry[i] for i in range(n.value)]
+
+
+def launched_kernels(L, ctx, cap: int):
+    """Names of the kernels the timed LK calls launched, by entry
+    (lk_kernel_fw<10, true> where the forward entry ran the 10-unit no-tail build)."""
+    return sorted({kernel_of_tag(t) for t in timing_entries(L, ctx, cap)})
+
+
 def kernel_of_tag(tag: int) -> str:
-    """psn_lk_timing_launches tag -> kernel name (a call split over several
-    window-class launches: "mixed:" + the launch with the most window pixels)."""
+    """psn_lk_timing_launches / psn_lk_timing_entries tag -> kernel name (a call
+    split over several window-class launches: "mixed:" + the launch with the most
+    window pixels)."""
     if tag >= 1000:
         return "mixed:" + kernel_of_tag(tag - 1000)
     if tag == 3:
@@ -151,6 +168,8 @@ def kernel_of_tag(tag: int) -> str:
         return "lk_kernel_st"
     if tag == 2:
         return "lk_kernel"
+    if tag % 10 == 3:  # the forward entry of the no-tail build
+        return f"lk_kernel_fw<{tag // 10}, true>"
     if tag % 10 == 2:  # the two-wave build (128 threads)
         return f"lk_kernel_bx<{tag // 10}, true, 128>"
     return f"lk_kernel_bx<{tag // 10}, {'true' if tag % 10 else 'false'}>"
@@ -241,6 +260,7 @@ def load(path: str | None = None):
                                       ctypes.POINTER(ip), ctypes.POINTER(ctypes.c_double)]
     L.psn_lk_timing_launches.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ip),
                                          ctypes.POINTER(ip)]
+    L.psn_lk_timing_entries.argtypes = [vp, ip, ctypes.POINTER(ip), ctypes.POINTER(ip)]
     L.psn_lk_debug_set_stamps.argtypes = [vp, vp]
     L.psn_lk_debug_count_samples.argtypes = [vp, ip]
     L.psn_lk_debug_read_samples.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]

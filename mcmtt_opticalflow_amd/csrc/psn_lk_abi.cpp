@@ -460,6 +460,7 @@ int psn_lk_enable_timing(psn_lk_ctx *c, int capacity, int every) {
     }
     c->tcap = capacity;
     c->track_tag.assign((size_t)capacity, 0);
+    c->track_entry.assign((size_t)capacity, 0);
     c->every = every;
     return PSN_LK_OK;
 }
@@ -503,6 +504,14 @@ int psn_lk_timing_launches(psn_lk_ctx *c, int cap, double *ms, int *tag, int *n)
         ms[i] = t;
         tag[i] = c->track_tag[(size_t)i];
     }
+    *n = (int)k;
+    return PSN_LK_OK;
+}
+
+int psn_lk_timing_entries(psn_lk_ctx *c, int cap, int *entry, int *n) {
+    if (!c || cap < 0 || !n || (cap > 0 && !entry)) return PSN_LK_ERR_ARG;
+    const long k = std::min<long>(std::min<long>(c->t_track.n, c->tcap), cap);
+    for (long i = 0; i < k; i++) entry[i] = c->track_entry[(size_t)i];
     *n = (int)k;
     return PSN_LK_OK;
 }
@@ -804,7 +813,7 @@ static int launch_plan(psn_lk_ctx *c, const psn::LkLaunchPlan &L, const float *d
     }
     if (L.cls == psn::kClsBx) {
         a.poison_lds = c->poison_lds ? lds : 0;
-        HIPCHK(c, psn::launch_lk_bx(a, wgs, L.upt, L.notail, L.nt, lds, c->stream));
+        HIPCHK(c, psn::launch_lk_bx(a, wgs, L.upt, L.notail, L.nt, L.fw, lds, c->stream));
         return PSN_LK_OK;
     }
     if (L.cls == psn::kClsTiled) {
@@ -847,7 +856,10 @@ static int track_device_impl(psn_lk_ctx *c, const psn_lk_query *q, int nq, const
     if ((rc = psn::timer_begin(c, c->t_track, c->stream, ti))) return rc;
     for (const psn::LkLaunchPlan &L : plan.launches)
         if ((rc = launch_plan(c, L, d_prev, d_next, d_status, d_err, d_counts, count_stride))) return rc;
-    if (ti >= 0 && plan.tag) c->track_tag[(size_t)ti] = plan.tag;
+    if (ti >= 0 && plan.tag) {
+        c->track_tag[(size_t)ti] = plan.tag;
+        c->track_entry[(size_t)ti] = plan.entry;
+    }
     if ((rc = flush_pending(c))) return rc;  // no launch took it (no single-tile launch)
     if ((rc = psn::timer_end(c, c->t_track, c->stream, ti))) return rc;
     // the next build into these slots waits for this launch
@@ -970,6 +982,10 @@ int psn_lk_debug_set_variant(psn_lk_ctx *c, int key, int value) {
     case PSN_LK_VARIANT_BX_WAVES:
         if (value != 0 && value != 2 && value != 4) return PSN_LK_ERR_ARG;
         c->cfg.bx_waves = value;
+        return PSN_LK_OK;
+    case PSN_LK_VARIANT_FW:
+        if (value != 0 && value != 1 && value != 2) return PSN_LK_ERR_ARG;
+        c->cfg.fw = value;
         return PSN_LK_OK;
     default: return PSN_LK_ERR_ARG;
     }

@@ -134,6 +134,7 @@ struct psn_lk_ctx {
     int tcap = 0;
     CallTimer t_push, t_track;
     std::vector<int> track_tag;  // per timed track call: the kernel it ran (psn_lk_timing_launches)
+    std::vector<int> track_entry;  // ... and the entry of that kernel (psn_lk_timing_entries)
     int every = 1;               // time every `every`-th call of each kind
     std::string err;
 };

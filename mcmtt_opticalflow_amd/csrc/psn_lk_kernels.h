@@ -258,6 +258,14 @@ constexpr int kBxNT = 256;
 // of kBxTile2 threads so that six workgroups fit the CU's LDS as well.
 constexpr int kBxNT2 = 128;
 constexpr int kBxUPT2 = 8;
+// The forward entry (lk_kernel_fw<kBxFwUPT, true>, psn_lk_bx.hip): the body of
+// lk_kernel_bx<kBxFwUPT, true> behind a kernel of its own, for the no-tail windows
+// that build takes (more than 8 and at most kBxFwUPT units per thread: Tracker2D's
+// 64 x 160 forward windows). Same workgroup, launch bounds and LDS plan.
+constexpr int kBxFwUPT = 10;
+__host__ __device__ constexpr bool bx_fw_fits(int upt, bool notail, int nt) {
+    return upt == kBxFwUPT && notail && nt == kBxNT;
+}
 constexpr int kBxTile = 32, kBxTile2 = 16;  // threads per fallback tile granule
 constexpr int kBxMaxUPT = 16;
 constexpr int kBxRecInts = 8 * 15 + 4;                 // per wave and chain: {total, max, min prefix, -} at lanes 31 and 63; term flag
@@ -466,8 +474,9 @@ hipError_t launch_lk_st(const LkLaunchArgs &a, int total_wgs, int nt, int ept, i
 // Box-window kernel (psn_lk_bx.hip, PSN_BX_KERNELS) with UPT units per thread (4, 8, 10, 12 or 16).
 // notail: every query of the launch sums in the SSE2 order with width % 8 == 0
 // (no scalar-tail chain: a build without its per-pixel bookkeeping); nt: the
-// workgroup size (kBxNT, or kBxNT2 for the two-wave build <8, true>)
-hipError_t launch_lk_bx(const LkLaunchArgs &a, int total_wgs, int upt, bool notail, int nt, int lds_bytes,
+// workgroup size (kBxNT, or kBxNT2 for the two-wave build <8, true>); fw: the
+// forward entry lk_kernel_fw of that build (PSN_FW_KERNELS; bx_fw_fits)
+hipError_t launch_lk_bx(const LkLaunchArgs &a, int total_wgs, int upt, bool notail, int nt, bool fw, int lds_bytes,
                         hipStream_t s);
 // Large-window kernel (psn_lk_large.hip): `grid` workgroups over a.lk_wgs points.
 hipError_t launch_lk_lg(const LkLaunchArgs &a, int grid, int lds_bytes, int tq, hipStream_t s);

@@ -31,6 +31,13 @@ namespace {
 // The planner's default for the windows the two-wave box build fits
 // (PSN_LK_VARIANT_BX_WAVES 0); DESIGN.md section 8 has the measurement behind it.
 constexpr bool kBxPlanTwoWave = true;
+// ... and for the launches the forward entry fits (PSN_LK_VARIANT_FW 0): the
+// entry's gains are measured against lk_kernel_bx<10, true> in DESIGN.md section 8.
+// (PSN_BX_PLAN_FW=0: a build whose planner never takes it, for A/B runs of the benchmark)
+#ifndef PSN_BX_PLAN_FW
+#define PSN_BX_PLAN_FW 1
+#endif
+constexpr bool kBxPlanFw = PSN_BX_PLAN_FW != 0;
 
 // One query as planned: its device descriptor and the kernels that can take it.
 struct PlannedQuery {
@@ -341,6 +348,9 @@ void plan_launch(const PlanCfg &c, PlannedQuery *const *grp, int n, int cls, int
         L.upt = upt;
         L.notail = notail;
         L.nt = nt;
+        // the forward entry of the build: a launch-time choice (same queries, same
+        // LDS plan, same launch group and key)
+        L.fw = bx_fw_fits(upt, notail, nt) && (c.fw == 2 || (c.fw == 0 && kBxPlanFw));
         L.lds = lds_bx;
         return;
     }
@@ -376,6 +386,7 @@ int plan_call(const PlanCfg &cfg, const psn_lk_query *q, int nq, const char *fil
     out.launches.clear();
     out.used_slots.clear();
     out.tag = 0;
+    out.entry = 0;
     // plan every query first: a bad one fails the call before anything is launched
     std::vector<PlannedQuery> plan;
     plan.reserve((size_t)nq);
@@ -444,6 +455,9 @@ int plan_call(const PlanCfg &cfg, const psn_lk_query *q, int nq, const char *fil
     if (!groups.empty()) {
         const size_t dom = (size_t)(std::max_element(group_px.begin(), group_px.end()) - group_px.begin());
         out.tag = kernel_tag(groups[dom].first, groups[dom].second) + (groups.size() > 1 ? 1000 : 0);
+        bool fw = false;  // (a group's launches share their build, hence their entry)
+        for (const LkLaunchPlan &L : out.launches) fw |= L.cls == groups[dom].first && L.key == groups[dom].second && L.fw;
+        out.entry = entry_tag(groups[dom].first, groups[dom].second, fw) + (groups.size() > 1 ? 1000 : 0);
     }
     return PSN_LK_OK;
 }

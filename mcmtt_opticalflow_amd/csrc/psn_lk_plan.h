@@ -48,6 +48,9 @@ struct PlanCfg {
     // BX_WAVES: 0 = planner, 4 = never the two-wave box build, 2 = the two-wave
     // build wherever it fits (psn::bx_two_wave_fits)
     int bx_waves = 0;
+    // FW: 0 = planner, 1 = never the forward entry (lk_kernel_fw), 2 = the forward
+    // entry wherever it fits (psn::bx_fw_fits)
+    int fw = 0;
     // TILED_LDS: LDS budget of a tiled-kernel workgroup (bytes); 76 KB keeps two
     // workgroups per CU (Tracker2D box windows: 64x64 backward, 64x160 forward at 1080p)
     int tiled_lds = 76 * 1024;
@@ -64,6 +67,10 @@ enum LkClass { kClsSt = 0, kClsBx = 1, kClsTiled = 2, kClsLg = 3 };
 
 // The kernel a launch runs, as psn_lk_timing_launches reports it.
 inline int kernel_tag(int cls, int key) { return cls == kClsBx ? key : cls == kClsSt ? 1 : cls == kClsTiled ? 2 : 3; }
+// ... and the entry that runs it, as psn_lk_timing_entries reports it: the
+// kernel's tag, but 10 * units per thread + 3 for a box build on its forward
+// entry (lk_kernel_fw)
+inline int entry_tag(int cls, int key, bool fw) { return cls == kClsBx && fw ? key - key % 10 + 3 : kernel_tag(cls, key); }
 
 // One launch as planned: everything but pointers and HIP calls.
 struct LkLaunchPlan {
@@ -80,6 +87,7 @@ struct LkLaunchPlan {
     int ept = 0, ow_e = 0, occ = 1;  // lk_kernel_st<nt, ept, ow_e, occ>
     int upt = 0;                   // lk_kernel_bx: units per thread
     bool notail = false;           // + its no-tail build
+    bool fw = false;               // + its forward entry, lk_kernel_fw<upt, notail, nt>
     // lk_kernel_lg<key>: int2s of one HBM window slot; the grid strides over the points
     long long lg_slot = 0;
     int grid = 0;
@@ -95,6 +103,8 @@ struct LkCallPlan {
     // kernel_tag of the (class, key) group with the most window pixels, + 1000
     // when the call has several groups; 0: nothing to launch
     int tag = 0;
+    // the same with entry_tag: which entry of that kernel runs
+    int entry = 0;
 };
 
 // HBM budget of one stream's large-window slots: one slot per point up to it,

@@ -9,6 +9,7 @@ the chain lane's time split four ways for the A and the b fallback.
 STAMPS_LIB=path runs another stamps build (make ... EXTRA=-DPSN_BX_GEO_NT=0).
 
   WIN=64 WINH=160 NPTS=630 python tools/bx_stamps.py
+  WIN=64 WINH=160 NPTS=2048 VARIANTS=fw=1 python tools/bx_stamps.py        # lk_kernel_bx<10, true>, not its forward entry lk_kernel_fw
   WIN=64 WINH=64 NPTS=2048 VARIANTS=bx_waves=4 python tools/bx_stamps.py   # the four-wave build; bx_waves=2:
                                                                             # the two-wave lk_kernel_bx<8, true, 128>
 """
@@ -50,7 +51,7 @@ def main():
         L.psn_lk_enable_timing(ctx.handle, 2, 1)
         ctx.track([q], pts)
         ctx.sync()
-        kernels = sorted({_lib.kernel_of_tag(t) for _, t in _lib.timing_launches(L, ctx.handle, 2)})
+        kernels = _lib.launched_kernels(L, ctx.handle, 2)
         s = st.to_array((npts, 64), np.uint64).astype(np.int64)
     tot = s[:, 15]
     slow = int(np.argmax(tot))
@@ -72,7 +73,7 @@ def main():
     # workgroup barrier, or the tile's ready flag in the flag hand-off loop). The
     # cycles per term are over a full tile's terms per chain (tile threads x units
     # per thread, one half-wave granule per tile).
-    m = re.search(r"lk_kernel_bx<(\d+), true(?:, (\d+))?>", out["kernel"])
+    m = re.search(r"lk_kernel_(?:bx|fw)<(\d+), true(?:, (\d+))?>", out["kernel"])
     terms = int(m.group(1)) * (16 if m.group(2) == "128" else 32) if m else None
 
     def split(n, geo, first, chain, wait, extra=None):
@@ -92,6 +93,12 @@ def main():
     out["a_fallback_per_tile"] = split(c[4], c[1], c[5], c[2], c[3], {"own_wave_next_tile_write": c[0]})
     if s[:, 28].sum() > 0:  # the flag hand-off loop (four-wave builds, half-wave tiles)
         out["b_fallback_per_tile"] = split(c[9], c[7], c[11], c[8], c[6]) | {"loop": "flags"}
+        # the flag wait by tile index: the first tile of a fallback pass against the later ones (stamps 31 / 32)
+        w1, n1 = float(s[:, 31].sum()), float(s[:, 32].sum())
+        out["b_flag_wait_by_tile_index"] = {
+            "passes_per_workgroup": round(n1 / npts, 2), "first_tile": round(w1 / max(n1, 1.0), 1),
+            "later_tiles": round((float(c[6]) - w1) / max(float(c[9]) - n1, 1.0), 1),
+            "first_tile_share_of_wait": round(w1 / max(float(c[6]), 1.0), 3)}
     else:
         out["b_fallback_per_tile"] = split(s[:, 14].sum(), s[:, 12].sum() - c[10], c[11], c[10], s[:, 13].sum()) | {"loop": "barrier"}
     it = max(s[:, 10].sum(), 1)

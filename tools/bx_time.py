@@ -8,6 +8,7 @@ the median / mean over `--reps` launches and a checksum of the outputs (the
 same checksum across builds = the same results).
 
   python tools/bx_time.py --reps 40
+  python tools/bx_time.py --shapes 64x160 --variants fw=1        # lk_kernel_bx<10, true>, not its forward entry lk_kernel_fw
   python tools/bx_time.py --shapes 64x64 --variants bx_waves=4   # the four-wave build of a two-wave window
   python tools/bx_time.py --shapes 64x64 --variants bx_waves=2   # lk_kernel_bx<8, true, 128>
 """
@@ -52,7 +53,7 @@ def main():
                 res = ctx.track([q], pts)
             timed = _lib.timing_launches(L, ctx.handle, args.reps + 1)
             ms = np.array([m for m, _ in timed])
-            kernels = sorted({_lib.kernel_of_tag(t) for _, t in timed})
+            kernels = _lib.launched_kernels(L, ctx.handle, args.reps + 1)
             L.psn_lk_enable_timing(ctx.handle, 0, 1)
             dig = hashlib.sha1(b"".join(np.ascontiguousarray(a).tobytes() for a in res)).hexdigest()[:16]
             out[shape] = {"median_us": round(1e3 * float(np.median(ms)), 1), "mean_us": round(1e3 * float(ms.mean()), 1),

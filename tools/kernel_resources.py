@@ -58,12 +58,13 @@ def kernels(lib):
 def pretty(mangled):
     """The box kernel's builds by the name _lib.kernel_of_tag gives their launches:
     lk_kernel_bx<8, true, 128> for _ZN3psn12lk_kernel_bxILi8ELb1ELi128EEEvNS_12LkLaunchArgsE (the
-    builds of 256 threads drop the default size); other kernels keep the mangled name."""
-    m = re.search(r"lk_kernel_bxILi(\d+)ELb([01])ELi(\d+)E", mangled)
+    builds of 256 threads drop the default size), the forward entry lk_kernel_fw likewise;
+    other kernels keep the mangled name."""
+    m = re.search(r"lk_kernel_(bx|fw)ILi(\d+)ELb([01])ELi(\d+)E", mangled)
     if not m:
         return mangled
-    upt, notail, nt = int(m.group(1)), m.group(2) == "1", int(m.group(3))
-    return f"lk_kernel_bx<{upt}, {'true' if notail else 'false'}" + (">" if nt == 256 else f", {nt}>")
+    upt, notail, nt = int(m.group(2)), m.group(3) == "1", int(m.group(4))
+    return f"lk_kernel_{m.group(1)}<{upt}, {'true' if notail else 'false'}" + (">" if nt == 256 else f", {nt}>")
 
 
 def kernel_text(lib, rx):

@@ -35,9 +35,11 @@ def short(name):
     # (by the name _lib.kernel_of_tag and kernel_resources.pretty give them: the
     # builds of 256 threads drop the default workgroup size, the two-wave build
     # keeps its 128 -- "lk_kernel_bx<10, true>", "lk_kernel_bx<8, true, 128>")
-    i = name.find("lk_kernel_bx<")
-    if i >= 0:
-        return re.sub(r", 256>$", ">", name[i:name.index(">", i) + 1])
+    # (the forward entry lk_kernel_fw the same way: "lk_kernel_fw<10, true>")
+    for fam in ("lk_kernel_bx<", "lk_kernel_fw<"):
+        i = name.find(fam)
+        if i >= 0:
+            return re.sub(r", 256>$", ">", name[i:name.index(">", i) + 1])
     for k in ("lk_kernel_st", "lk_kernel_lg", "lk_kernel", "pyramid_kernel", "read_u8", "read_x4", "write_u8",
               "write_x4"):
         if k in name:

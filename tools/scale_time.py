@@ -101,7 +101,9 @@ def child_run(a):
         step(t)
     hip.synchronize()
     per = {}
-    for ms, tag in _lib.timing_launches(L, lkh, 8 * measure + 64):
+    # (by entry: lk_kernel_fw<10, true> where the forward entry ran)
+    timed = _lib.timing_launches(L, lkh, 8 * measure + 64)
+    for (ms, _), tag in zip(timed, _lib.timing_entries(L, lkh, 8 * measure + 64)):
         k = _lib.kernel_of_tag(tag)
         n, tot = per.get(k, (0, 0.0))
         per[k] = (n + 1, tot + ms)
