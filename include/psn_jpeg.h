@@ -21,9 +21,12 @@
  *                    from a cold state, exit states are handed to the successor
  *                    until none changes (Huffman streams synchronise themselves),
  *                    then a prefix sum places the blocks and a last pass writes
- *                    them. Its output is the serial path's, byte for byte. Results are bit-identical to libjpeg-turbo's decoder (the one PIL links)
- * -- see oracle/jpeg_oracle.c for the pinning and for where OpenCV 2.4.6's
- * bundled libjpeg 8 differs (subsampled chroma).
+ *                    them. Its output is the serial path's, byte for byte.
+ * Results are bit-identical to oracle/jpeg_oracle.c, and to libjpeg-turbo's
+ * decoder (the one PIL links) for intact files whose samples stay in range --
+ * see oracle/jpeg_oracle.c for the pinning, for truncated files and out-of-range
+ * samples, and for where OpenCV 2.4.6's bundled libjpeg 8 differs (subsampled
+ * chroma).
  *
  * Plain C; returns 0 (PSN_LK_OK) or a negative PSN_LK_ERR_* code.
  */
@@ -100,6 +103,13 @@ int psn_jpeg_last_stats(psn_jpeg_ctx *ctx, psn_jpeg_stats *out);
  * multiple of 4 in [4, 1024]. */
 #define PSN_JPEG_DEFAULT_SUB_BYTES 64 /* measured 64 / 128 / 256 at 1080p: DESIGN section 4 */
 int psn_jpeg_debug_set_entropy(psn_jpeg_ctx *ctx, int mode, int sub_bytes);
+/* The coefficients of the context's last decode as its IDCT read them:
+ * [blocks][64] int16 in natural order, DC prediction applied, the layout of
+ * psn_jpeg_entropy_model's coef. Waits for the decoder's stream. `count` is the
+ * number of int16 values `out` holds and must be 64 times the scan's block
+ * count (psn_jpeg_entropy_model's stats->blocks with coef NULL); PSN_LK_ERR_ARG
+ * otherwise, or when nothing has been decoded. */
+int psn_jpeg_debug_read_coefficients(psn_jpeg_ctx *ctx, int16_t *out, size_t count);
 
 /* CPU model of the entropy decode (host only): the symbol step the kernels run
  * (csrc/psn_jpeg_entropy.h) with the kernels' rounds emulated sequentially.

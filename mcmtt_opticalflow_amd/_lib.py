@@ -247,6 +247,8 @@ def load(path: str | None = None):
         L.psn_jpeg_last_stats.argtypes = [vp, ctypes.POINTER(JpegStats)]
         L.psn_jpeg_entropy_model.argtypes = [vp, ctypes.c_size_t, ip, ip, vp, ctypes.POINTER(JpegStats)]
         L.psn_lk_jpeg_last_stats.argtypes = [vp, ctypes.POINTER(JpegStats)]
+    if hasattr(L, "psn_jpeg_debug_read_coefficients"):
+        L.psn_jpeg_debug_read_coefficients.argtypes = [vp, vp, ctypes.c_size_t]
     L.psn_lk_debug_set_variant.argtypes = [vp, ip, ip]
     L.psn_lk_track.argtypes = [vp, ctypes.POINTER(LkQuery), ip, fp, fp, u8p, fp]
     L.psn_lk_track_device.argtypes = [vp, ctypes.POINTER(LkQuery), ip, vp, vp, vp, vp]

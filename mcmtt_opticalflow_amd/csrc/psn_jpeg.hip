@@ -139,7 +139,8 @@ struct BitReader {
                 return h.vals[(code + h.valoff[l]) & 255];
             }
         }
-        skip(16);  // corrupt data: libjpeg warns and yields 0
+        (void)peek(17);  // corrupt data: libjpeg has read a 17th bit when it warns and yields 0
+        skip(17);
         return 0;
     }
 };
@@ -608,6 +609,7 @@ struct psn_jpeg_ctx {
     size_t par_cap = 0;
     psn_jpeg_stats last{};          // the last decode (host part; the kernels' counters are in d_par)
     bool decoded = false;
+    int last_nblocks = 0;           // coefficient blocks of the last decode (psn_jpeg_debug_read_coefficients)
     std::string err;
 };
 
@@ -1052,6 +1054,7 @@ int psn_jpeg_decode_device(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uin
     plan_entropy(P, c->ent_mode, c->ent_sub, pl);
     c->last = psn_jpeg_stats{pl.path, pl.segments, pl.sub_bytes, pl.subsequences, pl.sequences, 0, 0, 0};
     c->decoded = true;
+    c->last_nblocks = a.nblocks;
     if (pl.path == PSN_JPEG_PATH_PARALLEL) {
         const size_t nsub = (size_t)pl.subsequences, nseq = (size_t)pl.sequences;
         auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
@@ -1146,6 +1149,17 @@ int psn_jpeg_debug_set_entropy(psn_jpeg_ctx *c, int mode, int sub_bytes) {
         return jerr(c, PSN_LK_ERR_ARG, "entropy mode %d (0..2), sub_bytes %d (0 or a multiple of 4 in [4, 1024])", mode, sub_bytes);
     c->ent_mode = mode;
     c->ent_sub = sub_bytes;
+    return PSN_LK_OK;
+}
+
+int psn_jpeg_debug_read_coefficients(psn_jpeg_ctx *c, int16_t *out, size_t count) {
+    if (!c || !out) return PSN_LK_ERR_ARG;
+    if (!c->decoded) return jerr(c, PSN_LK_ERR_ARG, "nothing decoded yet");
+    if (count != (size_t)c->last_nblocks * 64)
+        return jerr(c, PSN_LK_ERR_ARG, "count %zu is not %d blocks * 64", count, c->last_nblocks);
+    JCHK(c, hipSetDevice(c->device));
+    JCHK(c, hipMemcpyAsync(out, c->d_coef, count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    JCHK(c, hipStreamSynchronize(c->stream));
     return PSN_LK_OK;
 }
 

@@ -115,7 +115,7 @@ struct Reader {
         skip((int)(pos & 7));
     }
     PSN_JENT_HD uint64_t pos() const { return (uint64_t)(rp * 8 - n - 8 * popc64(mk)); }
-    // step() fills once per symbol: a symbol reads at most 16 + 15 of the >= 57 bits
+    // step() fills once per symbol: a symbol reads at most 16 + 15 (a code no length accepts: 17) of the >= 57 bits
     PSN_JENT_HD unsigned peek(int k) const { return (unsigned)(buf >> (64 - k)); }
     PSN_JENT_HD void skip(int k) {
         buf <<= k;
@@ -142,7 +142,9 @@ struct Reader {
                 return h.vals[(code + h.valoff[l]) & 255];
             }
         }
-        skip(16);  // corrupt code: skip 16, value 0
+        // a code no length accepts: jpeg_huff_decode has read a 17th bit by the time
+        // its sentinel maxcode[17] ends the search; value 0
+        skip(17);
         return 0;
     }
 };

@@ -437,6 +437,15 @@ class JpegDecoder:
             raise PsnLkError(rc, f"psn_jpeg_last_stats: {self._L.psn_jpeg_last_error(self._h).decode()}")
         return _lib.struct_dict(s)
 
+    def coefficients(self) -> np.ndarray:
+        """psn_jpeg_debug_read_coefficients: the last decode's (blocks, 64) int16
+        coefficients as the IDCT read them (natural order, DC prediction applied)."""
+        coef = np.empty((self.stats()["blocks"], 64), np.int16)  # every block of the scan is decoded
+        rc = self._L.psn_jpeg_debug_read_coefficients(self._h, coef.ctypes.data, coef.size)
+        if rc != 0:
+            raise PsnLkError(rc, f"psn_jpeg_debug_read_coefficients: {self._L.psn_jpeg_last_error(self._h).decode()}")
+        return coef
+
     @staticmethod
     def plan(data: bytes) -> dict:
         """psn_jpeg_entropy_plan: the planner's choice for a file (host only)."""

@@ -18,6 +18,14 @@
  * instead of the triangle filter: for 4:2:0 / 4:2:2 frames that decoder is not
  * present here and parity with it is unpinned; 4:4:4 and grayscale frames
  * decode the same in both.
+ *
+ * The pinning holds for intact files whose samples stay in range. After the
+ * data ends this decoder (and the device) keeps decoding zero bits, and
+ * libjpeg-turbo's output for a truncated file differs from that; its SIMD IDCT
+ * is exact only for in-range samples (coefficients of +-1023 everywhere, or a
+ * quantiser of 255, give other pixels there). For such files this restatement
+ * of jdhuff.c and jidctint.c is itself the reference
+ * (tests/test_jpeg_synth.py, tests/test_jpeg_synth_gpu.py).
  */
 #include <stdint.h>
 #include <stdlib.h>
