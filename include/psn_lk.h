@@ -47,6 +47,17 @@ extern "C" {
 #define PSN_LK_USE_INITIAL_FLOW 4      /* cv::OPTFLOW_USE_INITIAL_FLOW */
 #define PSN_LK_GET_MIN_EIGENVALS 8     /* cv::OPTFLOW_LK_GET_MIN_EIGENVALS */
 #define PSN_LK_ACCUM_SCALAR 0x100      /* float sums in the scalar build's order (default: SSE2 build) */
+/* For a caller that requests err only for what it does to status: OpenCV's level-0
+ * bounds re-check, win_outside(cv_floor(nextPt - halfWin), ...) -> status = 0, runs
+ * only when err is requested (Tracker2D: PSNWhere_Tracker2D.cpp:781, :876, which
+ * never reads the values). With this flag and err != NULL, status and next_xy are
+ * exactly those of the same call without it, and the CONTENTS of err[] are
+ * unspecified: the kernels that honour it run the re-check alone and skip the
+ * window pass that sums |J - I|. A kernel may ignore the flag (it then writes the
+ * err values). Ignored with PSN_LK_GET_MIN_EIGENVALS: err is the minimum
+ * eigenvalue as ever. An added flag bit: PSN_LK_ABI_VERSION stays (it counts
+ * changes to what existing callers get, not additions). */
+#define PSN_LK_ERR_STATUS_ONLY 0x200
 
 /* cv::TermCriteria type bits */
 #define PSN_LK_TERM_COUNT 1
@@ -298,6 +309,8 @@ int psn_lk_timing_entries(psn_lk_ctx *ctx, int cap, int *entry, int *n);
  *                              2 = the forward entry for every launch it fits (the
  *                              no-tail build of 10 units per thread: windows of
  *                              2,049 - 2,560 units of 4 px, Tracker2D's 64 x 160)
+ *   PSN_LK_VARIANT_ERR_STATUS  0 = PSN_LK_ERR_STATUS_ONLY is honoured by the kernels that
+ *                              take it; 1 = the flag is ignored (every launch writes err)
  * Queries are split into one launch per window class (single-tile / box kernel
  * per units-per-thread and tail build / row-tiled / large), each sized for its
  * own windows. */
@@ -314,6 +327,7 @@ int psn_lk_timing_entries(psn_lk_ctx *ctx, int cap, int *entry, int *n);
 #define PSN_LK_VARIANT_POISON_LDS 11
 #define PSN_LK_VARIANT_BX_WAVES 12
 #define PSN_LK_VARIANT_FW 13
+#define PSN_LK_VARIANT_ERR_STATUS 14
 int psn_lk_debug_set_variant(psn_lk_ctx *ctx, int key, int value);
 
 /* Window-sample counter (SURVEY 8(d)'s compute figure): while on, every box-

@@ -33,6 +33,7 @@ ERRORS = {
 USE_INITIAL_FLOW = 4
 GET_MIN_EIGENVALS = 8
 ACCUM_SCALAR = 0x100
+ERR_STATUS_ONLY = 0x200  # err requested for its level-0 bounds re-check alone: err[] unspecified
 OVERLAP_OFF, OVERLAP_STREAM, OVERLAP_FUSED = 0, 1, 2  # psn_lk_set_ingest_overlap modes
 TERM_COUNT = 1
 TERM_EPS = 2
@@ -40,7 +41,8 @@ MAX_WIN_WIDTH = 6400  # PSN_LK_MAX_WIN_WIDTH (any window height)
 COMM_UNIQUE_ID_BYTES = 128
 # psn_lk_debug_set_variant keys (tests / experiments; never read from the environment)
 VARIANTS = {"threads": 1, "generic": 2, "onewave": 3, "box": 4, "tiled_lds": 5, "fused_helpers": 6,
-            "large": 7, "lg_lds": 8, "lg_jr": 9, "st_ovl": 10, "poison_lds": 11, "bx_waves": 12, "fw": 13}
+            "large": 7, "lg_lds": 8, "lg_jr": 9, "st_ovl": 10, "poison_lds": 11, "bx_waves": 12, "fw": 13,
+            "err_status": 14}
 
 
 class PsnLkError(RuntimeError):

@@ -987,6 +987,7 @@ int psn_lk_debug_set_variant(psn_lk_ctx *c, int key, int value) {
         if (value != 0 && value != 1 && value != 2) return PSN_LK_ERR_ARG;
         c->cfg.fw = value;
         return PSN_LK_OK;
+    case PSN_LK_VARIANT_ERR_STATUS: c->cfg.err_status_ignore = value != 0; return PSN_LK_OK;
     default: return PSN_LK_ERR_ARG;
     }
 }

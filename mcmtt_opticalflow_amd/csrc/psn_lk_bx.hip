@@ -35,7 +35,8 @@ namespace psn {
 // b fallback, flag loop 25 flag wait, 26 geometry + pad, 27 chain sums, 28 tiles;
 // barrier loop 29 chain sums (inside 12); 30 first-block wait of either loop;
 // 31 / 32 the flag wait and the count of the FIRST tile of each flag-loop pass
-// (inside 25 / 28).
+// (inside 25 / 28). stamps[wg][33]: the err pass of level 0, from after its bounds
+// re-check to the end (0 when it did not run: no err, PSN_LK_ERR_STATUS_ONLY).
 // NT: the workgroup size. kBxNT2 is the two-wave build (QT below): the same
 // kernel with two waves' records, err partials and staging strides, and fallback
 // tiles of a quarter wave (kBxTile2 threads), each written by its whole wave.
@@ -48,9 +49,14 @@ struct BxBasePolicy {
     // the half-wave tile writers (writeA_nt, write_tile_nt) take the division-free
     // tile geometry of the no-tail builds
     static constexpr bool kShortWriterGeo = false;
+    // PSN_LK_ERR_STATUS_ONLY ends level 0 after the bounds re-check (no err pass).
+    // Off here: the pinned builds keep their code; the two-wave build takes the
+    // flag through its own condition (QT in the body)
+    static constexpr bool kErrStatusOnly = false;
 };
 struct BxFwPolicy {
     static constexpr bool kShortWriterGeo = true;
+    static constexpr bool kErrStatusOnly = true;
 };
 
 template <int UPT, bool NOTAIL, int NT = kBxNT>

@@ -88,7 +88,7 @@
     float errv = 0.f;
     int par = 0;
 #ifdef PSN_LK_STAMPS
-    unsigned long long bx_acc[16] = {}, bx_t = 0, bx_t0 = 0, bx_r0 = 0;
+    unsigned long long bx_acc[16] = {}, bx_t = 0, bx_t0 = 0, bx_r0 = 0, bx_te = 0;
     // the fallback tile splits (stamps 19-30) add up in the 16 free words of the
     // scratch region, by thread 0 alone: as registers they spill in every build
     unsigned *bx_tl = (unsigned *)(RS + 32);
@@ -1077,6 +1077,11 @@
                 status = 0;
                 continue;
             }
+            // PSN_LK_ERR_STATUS_ONLY: the re-check above was all of err the caller
+            // wanted (err[] = 0); the builds held to their register counts ignore it
+            if constexpr (POL::kErrStatusOnly || QT)
+                if (flags & PSN_LK_ERR_STATUS_ONLY) continue;
+            PSN_CLK_ORDERED(bx_te);  // stamp 33: the err pass (from here to the level's end)
             int w00, w01, w10, w11;
             bilin_weights(__fsub_rn(qx, (float)iqx), __fsub_rn(qy, (float)iqy), w00, w01, w10, w11);
             if (!(jr_covers(iqx, iqy, w, h, jr_x0, jr_y0, JRW, JRH))) {
@@ -1156,6 +1161,7 @@
         unsigned long long t_end;
         PSN_CLK_ORDERED(t_end);
         bx_acc[15] = t_end - bx_t0;
+        if (bx_te) bx_te = t_end - bx_te;  // (level 0 is the last level: the pass ends here)
         unsigned long long r1;
         unsigned hwid, xcc;
         asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r1) : : "memory");
@@ -1164,6 +1170,7 @@
         if (tid == 0 && A.stamps) {  // thread 0: also the chain lane of the tile stamps 12-14
             for (int i = 0; i < 16; i++) A.stamps[(size_t)g * 64 + i] = bx_acc[i];
             for (int i = 19; i < 33; i++) A.stamps[(size_t)g * 64 + i] = bx_tl[i - 19];  // fallback tile splits
+            A.stamps[(size_t)g * 64 + 33] = bx_te;  // the err pass (0: not run)
             // residency: realtime (100 MHz) start / end and the CU it ran on
             A.stamps[(size_t)g * 64 + 16] = bx_r0;
             A.stamps[(size_t)g * 64 + 17] = r1;

@@ -333,6 +333,10 @@ __global__ __launch_bounds__(NT) void lk_kernel(LkLaunchArgs A) {
                 __syncthreads();
                 continue;
             }
+            if (flags & PSN_LK_ERR_STATUS_ONLY) {  // the re-check was all: err[] = 0
+                __syncthreads();
+                continue;
+            }
             bilin_weights(__fsub_rn(qx, (float)iqx), __fsub_rn(qy, (float)iqy), iw00, iw01, iw10, iw11);
             if (!(jr_valid && jr_covers(iqx, iqy, w, h, jr_x0, jr_y0, JRW, JRH))) {
                 jr_x0 = iqx - kJMargin;

@@ -879,6 +879,7 @@ __global__ __launch_bounds__(kLgNT, PSN_LG_WAVES) void lk_kernel_lg(LkLaunchArgs
                     status = 0;
                     continue;
                 }
+                if (flags & PSN_LK_ERR_STATUS_ONLY) continue;  // the re-check was all: err[] = 0
                 int w00, w01, w10, w11;
                 bilin_weights(__fsub_rn(qxf, (float)iqx), __fsub_rn(qyf, (float)iqy), w00, w01, w10, w11);
                 const LgJ JJ = window_j(iqx, iqy, w00, w01, w10, w11);

@@ -145,7 +145,7 @@ int plan_query(const PlanCfg &c, const char *filled, const psn_lk_query &q, bool
     d.win_h = h;
     d.max_level = ml;
     d.max_count = max_count;
-    d.flags = p.flags;
+    d.flags = c.err_status_ignore ? p.flags & ~PSN_LK_ERR_STATUS_ONLY : p.flags;
     d.tile_rows = pq.single ? h : pq.tiled_tr;
     d.min_eig = (float)p.min_eig_threshold;
     d.eps2 = eps * eps;

@@ -14,6 +14,11 @@
 #ifndef PSN_ST_OVL_DEFAULT
 #define PSN_ST_OVL_DEFAULT 1
 #endif
+// the default of the ERR_STATUS variant (0: a build that ignores the flag, for A/B
+// runs of the benchmark, which sets no variants)
+#ifndef PSN_LK_PLAN_ERR_STATUS
+#define PSN_LK_PLAN_ERR_STATUS 1
+#endif
 
 namespace psn {
 
@@ -51,6 +56,9 @@ struct PlanCfg {
     // FW: 0 = planner, 1 = never the forward entry (lk_kernel_fw), 2 = the forward
     // entry wherever it fits (psn::bx_fw_fits)
     int fw = 0;
+    // ERR_STATUS: 1 = PSN_LK_ERR_STATUS_ONLY is dropped from every query's flags
+    // (the launches write err as without it)
+    bool err_status_ignore = PSN_LK_PLAN_ERR_STATUS == 0;
     // TILED_LDS: LDS budget of a tiled-kernel workgroup (bytes); 76 KB keeps two
     // workgroups per CU (Tracker2D box windows: 64x64 backward, 64x160 forward at 1080p)
     int tiled_lds = 76 * 1024;

@@ -998,7 +998,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                     const int iqx = cv_floor(qx), iqy = cv_floor(qy);
                     if (win_outside(iqx, iqy, w, h, cols, rows)) {
                         status = 0;
-                    } else {
+                    } else if ((flags & PSN_LK_ERR_STATUS_ONLY) == 0) {  // (else the re-check was all: err[] = 0)
                         int iw00, iw01, iw10, iw11;
                         bilin_weights(__fsub_rn(qx, (float)iqx), __fsub_rn(qy, (float)iqy), iw00, iw01, iw10, iw11);
                         if (!(jr_covers(iqx, iqy, w, h, jr_x0, jr_y0, JRW, JRH))) {
@@ -1201,6 +1201,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                 status = 0;
                 continue;
             }
+            if (flags & PSN_LK_ERR_STATUS_ONLY) continue;  // the re-check was all: err[] = 0
             int iw00, iw01, iw10, iw11;
             bilin_weights(__fsub_rn(qx, (float)iqx), __fsub_rn(qy, (float)iqy), iw00, iw01, iw10, iw11);
             __syncthreads();  // every wave is done with R (last products) and JP

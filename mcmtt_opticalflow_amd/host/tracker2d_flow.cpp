@@ -186,7 +186,8 @@ int Tracker2DFlow::StepsAvailable(size_t cam) const {
 
 // One launch for all jobs: points concatenated, one query per job. err is
 // requested as the reference does (:781, :876): its bounds re-check can clear
-// status.
+// status. The err values are never read (Query sets PSN_LK_ERR_STATUS_ONLY:
+// err_out_ is what the re-check needs to run, its contents are unspecified).
 int Tracker2DFlow::RunJobs(std::vector<Job> &jobs) {
     size_t n = 0;
     queries_.clear();

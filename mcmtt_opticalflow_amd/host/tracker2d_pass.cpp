@@ -27,7 +27,12 @@ void Tracker2DFlow::Chk(hipError_t e, const char *what, int &rc) {
 
 // A calcOpticalFlowPyrLK call with the reference's defaults -- maxLevel 3,
 // (COUNT|EPS, 30, 0.01), minEig 1e-4 -- and the default window, which every
-// caller with points to track replaces (:782, :877).
+// caller with points to track replaces (:782, :877). Every Tracker2D launch is
+// built from this query (chain steps, forward, RunJobs, LaunchForwardFromChains)
+// and passes an err array, as the reference does (:781, :876), for the level-0
+// bounds re-check that err brings with it; the reference only clears and passes
+// featureErrors / pointError and nothing here reads an err value, so the queries
+// ask for the re-check alone (PSN_LK_ERR_STATUS_ONLY).
 psn_lk_query Tracker2DFlow::Query(int prev_slot, int next_slot, size_t first_pt, size_t num_pts) {
     psn_lk_query q;
     q.prev_slot = prev_slot;
@@ -35,6 +40,7 @@ psn_lk_query Tracker2DFlow::Query(int prev_slot, int next_slot, size_t first_pt,
     q.first_pt = (int)first_pt;
     q.num_pts = (int)num_pts;
     psn_lk_default_params(&q.params);
+    q.params.flags |= PSN_LK_ERR_STATUS_ONLY;
     return q;
 }
 

@@ -45,7 +45,7 @@ def main():
         ctx.push_frame(1, f1)
         rc = L.psn_lk_debug_set_stamps(ctx.handle, st.addr)
         assert rc == 0, "not a stamps build"
-        q = lk.make_query(1, 0, 0, npts, lk.make_params((w, h), 3))
+        q = lk.make_query(1, 0, 0, npts, lk.make_params((w, h), 3, flags=int(os.environ.get("FLAGS", "0"), 0)))
         for _ in range(3):
             ctx.track([q], pts)
         L.psn_lk_enable_timing(ctx.handle, 2, 1)
@@ -63,6 +63,10 @@ def main():
            "mean": {k: round(float(v), 1) for k, v in zip(PHASES, ph.mean(0))},
            "slowest_wg": {k: int(v) for k, v in zip(PHASES, ph[slow])} | {"iters": int(s[slow, 10]),
                                                                             "serial": int(s[slow, 11])}}
+    # stamp 33: the level-0 err pass behind its bounds re-check (FLAGS=0x200, PSN_LK_ERR_STATUS_ONLY: not run)
+    ran = s[:, 33] > 0
+    out["err_pass"] = {"workgroups": int(ran.sum()), "cycles_mean": round(float(s[ran, 33].mean()), 1) if ran.any() else 0.0,
+                       "share_of_wg_cycles": round(float(s[:, 33].sum() / max(tot.sum(), 1)), 4)}
     nt = max(s[:, 14].sum(), 1)
     out["serial_b_tiles_per_serial_iteration"] = round(float(s[:, 14].sum() / max(s[:, 11].sum(), 1)), 2)
     out["serial_b_per_tile_chain_lane_view"] = {"chain_sum": round(float(s[:, 12].sum() / nt), 1),
