@@ -31,50 +31,25 @@
 //          h2v1 / h2v2, edges replicated at the downsampled size), YCbCr->RGB
 //          (jdcolor.c, SCALEBITS 16), BGR out
 // Bit-identical to oracle/jpeg_oracle.c, which is pinned to libjpeg-turbo.
+//
+// This unit: the kernels with their device-only structs, the decoder context,
+// the launches and the entries of the ABI that touch the device. The host side
+// that needs no device is plain C++ beside it: psn_jpeg_parse.h / .cpp (marker
+// parser, Huffman table builder, entropy planner, the kernels' argument structs;
+// psn_jpeg_info, psn_jpeg_entropy_plan) and psn_jpeg_model.cpp (the CPU model of
+// the parallel path, psn_jpeg_entropy_model).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
 #include <string>
-#include <vector>
 
-#include "psn_jpeg.h"
-#include "psn_jpeg_entropy.h"  // HuffDev, the symbol step of the parallel path
-#include "psn_lk.h"
+#include "psn_jpeg_parse.h"  // Tables, CompGeo, JpegArgs, Parsed, parse(), the planner
 
 namespace psn {
 namespace {
-
-constexpr int kJpegMaxComp = 3;
-
-struct Tables {             // device copy per frame
-    uint16_t qt[4][64];     // natural order
-    HuffDev dc[4], ac[4];
-};
-
-struct CompGeo {
-    int h, v, tq, td, ta;   // sampling factors, table selectors
-    int bw, bh;             // blocks across / down (plane = bw*8 x bh*8)
-    int dw, dh;             // downsampled size (edges of the fancy upsampler)
-    int blk0;               // first coefficient block
-    int plane0;             // byte offset of the plane
-};
-
-struct JpegArgs {
-    int W, H, nc, hmax, vmax, mcux, nmcu, ri, nseg, data_len;
-    CompGeo c[kJpegMaxComp];
-    const Tables *tab;
-    const int *seg;          // byte offset of each segment's first entropy byte
-    const uint8_t *data;     // entropy-coded bytes
-    int16_t *coef;           // [blocks][64], natural order
-    uint8_t *planes;
-    uint8_t *out;
-    int out_stride;
-    int nblocks;
-};
 
 __constant__ int kNatural[64 + 16] = {
     0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -554,40 +529,6 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(JpegArgs A) {
     o[2] = clamp255(Y + r);
 }
 
-int rd16(const uint8_t *p) { return (p[0] << 8) | p[1]; }
-
-// jdhuff.c jpeg_make_d_derived_tbl: false for a table libjpeg rejects with
-// JERR_BAD_HUFF_TABLE -- more codes of a length than fit after the shorter ones
-// (the canonical code would overflow its length; the all-ones code is not
-// allowed), or a DC symbol above 15. Checked before any table entry is written.
-bool build_huff(const uint8_t *bits, const uint8_t *vals, int nvals, bool dc, HuffDev &h) {
-    for (int l = 1, code = 0; l <= 16; l++) {
-        code += bits[l - 1];
-        if (code >= (1 << l)) return false;
-        code <<= 1;
-    }
-    if (dc)
-        for (int i = 0; i < nvals; i++)
-            if (vals[i] > 15) return false;
-    memset(&h, 0, sizeof h);
-    int code = 0, k = 0;
-    for (int l = 1; l <= 16; l++) {
-        h.valoff[l] = k - code;
-        const int n = bits[l - 1];
-        for (int i = 0; i < n && l <= 9; i++) {  // lookahead entries of the codes of length <= 9
-            const int c = code + i, span = 1 << (9 - l);
-            for (int j = 0; j < span; j++) h.fast[(c << (9 - l)) | j] = (uint16_t)((l << 8) | vals[(k + i) & 255]);
-        }
-        code += n;
-        k += n;
-        h.maxcode[l] = n ? code - 1 : -1;
-        code <<= 1;
-    }
-    h.maxcode[17] = 0x7fffffff;
-    for (int i = 0; i < 256; i++) h.vals[i] = i < nvals ? vals[i] : 0;
-    return true;
-}
-
 }  // namespace
 }  // namespace psn
 
@@ -615,11 +556,6 @@ struct psn_jpeg_ctx {
 
 namespace {
 
-const int kNaturalHost[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-                              12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                              35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-                              58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
 int jerr(psn_jpeg_ctx *c, int code, const char *fmt, ...) {
     if (c) {
         char b[256];
@@ -632,327 +568,35 @@ int jerr(psn_jpeg_ctx *c, int code, const char *fmt, ...) {
     return code;
 }
 
-// A parsed frame: tables, geometry, entropy segments.
-struct Parsed {
-    psn::Tables tab;
-    psn::JpegArgs a{};
-    std::vector<int> seg;
-    size_t ent0 = 0, ent1 = 0;  // entropy bytes [ent0, ent1) of the file
-    // every 0xFF in [ent0, ent1) is followed by 0x00 and the last byte is not 0xFF:
-    // no fill bytes, no embedded marker (psn_jpeg_entropy.h reads such streams)
-    bool plain = true;
-    // per Huffman slot (class tc, index th): 0 never defined, 1 valid, -1 the last
-    // definition is one jpeg_make_d_derived_tbl rejects -- an error only for a table
-    // the scan uses (libjpeg builds the derived tables of the scan's components)
-    int hstate[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-};
+#define JCHK(c, e)                                                                                      \
+    do {                                                                                                \
+        hipError_t e_ = (e);                                                                            \
+        if (e_ != hipSuccess) return jerr((c), PSN_LK_ERR_HIP, "%s: %s", #e, hipGetErrorString(e_));   \
+    } while (0)
 
-int parse(const uint8_t *d, size_t n, Parsed &P, std::string &why) {
-    memset(&P.tab, 0, sizeof P.tab);
-    if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return why = "not a JPEG (no SOI)", PSN_LK_ERR_ARG;
-    int ids[psn::kJpegMaxComp] = {0, 0, 0};
-    bool sof = false;
-    size_t p = 2;
-    while (p + 4 <= n) {
-        if (d[p] != 0xFF) return why = "marker expected", PSN_LK_ERR_ARG;
-        const int m = d[p + 1];
-        if (m == 0xFF) {
-            p++;
-            continue;
-        }
-        const int len = psn::rd16(d + p + 2);
-        if (len < 2 || p + 2 + (size_t)len > n) return why = "truncated segment", PSN_LK_ERR_ARG;
-        const uint8_t *s = d + p + 4;
-        const int sl = len - 2;
-        if (m == 0xDB) {
-            for (int o = 0; o < sl;) {
-                const int pq = s[o] >> 4, tq = s[o] & 15;
-                if (tq > 3 || o + 1 + (pq ? 128 : 64) > sl) return why = "bad DQT", PSN_LK_ERR_ARG;
-                for (int i = 0; i < 64; i++)
-                    P.tab.qt[tq][kNaturalHost[i]] = (uint16_t)(pq ? psn::rd16(s + o + 1 + 2 * i) : s[o + 1 + i]);
-                o += 1 + (pq ? 128 : 64);
-            }
-        } else if (m == 0xC4) {
-            for (int o = 0; o < sl;) {
-                const int tc = s[o] >> 4, th = s[o] & 15;
-                if (tc > 1 || th > 3 || o + 17 > sl) return why = "bad DHT", PSN_LK_ERR_ARG;
-                int cnt = 0;
-                for (int l = 0; l < 16; l++) cnt += s[o + 1 + l];
-                if (cnt > 256 || o + 17 + cnt > sl) return why = "bad DHT", PSN_LK_ERR_ARG;
-                P.hstate[tc][th] = psn::build_huff(s + o + 1, s + o + 17, cnt, tc == 0, tc ? P.tab.ac[th] : P.tab.dc[th]) ? 1 : -1;
-                o += 17 + cnt;
-            }
-        } else if (m == 0xC0 || m == 0xC1) {
-            if (sl < 6 || s[0] != 8) return why = "not 8-bit", PSN_LK_ERR_UNSUPPORTED;
-            P.a.H = psn::rd16(s + 1);
-            P.a.W = psn::rd16(s + 3);
-            P.a.nc = s[5];
-            if ((P.a.nc != 1 && P.a.nc != 3) || sl < 6 + 3 * P.a.nc || !P.a.W || !P.a.H)
-                return why = "unsupported component count", PSN_LK_ERR_UNSUPPORTED;
-            for (int c = 0; c < P.a.nc; c++) {
-                ids[c] = s[6 + 3 * c];
-                P.a.c[c].h = s[7 + 3 * c] >> 4;
-                P.a.c[c].v = s[7 + 3 * c] & 15;
-                P.a.c[c].tq = s[8 + 3 * c] & 3;
-                if (P.a.c[c].h < 1 || P.a.c[c].h > 2 || P.a.c[c].v < 1 || P.a.c[c].v > 2)
-                    return why = "unsupported sampling", PSN_LK_ERR_UNSUPPORTED;
-            }
-            sof = true;
-        } else if ((m >= 0xC2 && m <= 0xCF) && m != 0xC4 && m != 0xC8 && m != 0xCC) {
-            return why = "not baseline sequential Huffman", PSN_LK_ERR_UNSUPPORTED;
-        } else if (m == 0xDD) {
-            P.a.ri = sl >= 2 ? psn::rd16(s) : 0;
-        } else if (m == 0xDA) {
-            if (!sof || sl < 1 || s[0] != P.a.nc) return why = "unsupported scan", PSN_LK_ERR_UNSUPPORTED;
-            for (int i = 0; i < P.a.nc; i++)
-                for (int c = 0; c < P.a.nc; c++)
-                    if (ids[c] == s[1 + 2 * i]) {
-                        P.a.c[c].td = (s[2 + 2 * i] >> 4) & 3;
-                        P.a.c[c].ta = s[2 + 2 * i] & 3;
-                    }
-            // the scan's tables (jdhuff.c start_pass_huff_decoder -> jpeg_make_d_derived_tbl:
-            // JERR_NO_HUFF_TABLE, JERR_BAD_HUFF_TABLE)
-            for (int c = 0; c < P.a.nc; c++)
-                for (int tc = 0; tc < 2; tc++) {
-                    const int st = P.hstate[tc][tc ? P.a.c[c].ta : P.a.c[c].td];
-                    if (st == 0) return why = "Huffman table not defined", PSN_LK_ERR_ARG;
-                    if (st < 0) return why = "bad DHT (code lengths or DC symbols)", PSN_LK_ERR_ARG;
-                }
-            P.ent0 = p + 2 + (size_t)len;
-            break;
-        }
-        p += 2 + (size_t)len;
-    }
-    if (!sof || !P.ent0) return why = "no frame / scan header", PSN_LK_ERR_ARG;
-    psn::JpegArgs &a = P.a;
-    a.hmax = a.vmax = 1;
-    for (int c = 0; c < a.nc; c++) {
-        a.hmax = std::max(a.hmax, a.c[c].h);
-        a.vmax = std::max(a.vmax, a.c[c].v);
-    }
-    // 4:4:4, 4:2:2 (h2v1) and 4:2:0 (h2v2) chroma; 4:4:0 (luma 1x2: a vertical-only
-    // upsample, h1v2) has no path in jpeg_color_kernel's chroma() and is refused
-    if (a.nc == 3 && (a.c[0].h != a.hmax || a.c[0].v != a.vmax || a.c[1].h != 1 || a.c[1].v != 1 || a.c[2].h != 1 ||
-                      a.c[2].v != 1 || (a.hmax == 1 && a.vmax == 2)))
-        return why = "unsupported sampling", PSN_LK_ERR_UNSUPPORTED;
-    const int mcux = (a.W + 8 * a.hmax - 1) / (8 * a.hmax), mcuy = (a.H + 8 * a.vmax - 1) / (8 * a.vmax);
-    int blk = 0, plane = 0;
-    for (int c = 0; c < a.nc; c++) {
-        psn::CompGeo &g = a.c[c];
-        g.bw = a.nc == 1 ? (a.W + 7) / 8 : mcux * g.h;
-        g.bh = a.nc == 1 ? (a.H + 7) / 8 : mcuy * g.v;
-        g.dw = (int)(((long long)a.W * g.h + a.hmax - 1) / a.hmax);
-        g.dh = (int)(((long long)a.H * g.v + a.vmax - 1) / a.vmax);
-        g.blk0 = blk;
-        g.plane0 = plane;
-        blk += g.bw * g.bh;
-        plane += g.bw * g.bh * 64;
-    }
-    a.nblocks = blk;
-    a.mcux = a.nc == 1 ? a.c[0].bw : mcux;
-    a.nmcu = a.nc == 1 ? a.c[0].bw * a.c[0].bh : mcux * mcuy;
-    // entropy data runs to EOI (or the end); restart segments start after each RSTn
-    P.seg.assign(1, 0);
-    size_t q = P.ent0;
-    while (q + 1 < n) {
-        if (d[q] == 0xFF && d[q + 1] != 0x00 && d[q + 1] != 0xFF) {
-            const int mk = d[q + 1];
-            if (mk >= 0xD0 && mk <= 0xD7) {
-                if (a.ri) P.seg.push_back((int)(q + 2 - P.ent0));
-                P.plain = false;  // a marker inside the entropy bytes
-                q += 2;
-                continue;
-            }
-            break;  // EOI or another marker ends the scan
-        }
-        if (d[q] == 0xFF && d[q + 1] == 0xFF) P.plain = false;  // a fill byte
-        q++;
-    }
-    P.ent1 = q;
-    if (P.ent1 > P.ent0 && d[P.ent1 - 1] == 0xFF) P.plain = false;
-    const int want = a.ri ? (a.nmcu + a.ri - 1) / a.ri : 1;
-    if ((int)P.seg.size() < want) return why = "missing restart markers", PSN_LK_ERR_ARG;
-    P.seg.resize((size_t)want);
-    a.nseg = want;
-    a.data_len = (int)(P.ent1 - P.ent0);
+// A device buffer of the context (with its pinned twin, if it has one) grown to
+// `to` bytes where it holds fewer than `need`: waits for the stream's work on the
+// old buffer first. After a failed allocation the pointer is null, the capacity 0.
+template <class T>
+int grow(psn_jpeg_ctx *c, T *&buf, size_t &cap, size_t need, size_t to, T **pinned = nullptr) {
+    if (cap >= need) return PSN_LK_OK;
+    JCHK(c, hipStreamSynchronize(c->stream));
+    if (buf) (void)hipFree(buf);
+    if (pinned && *pinned) (void)hipHostFree(*pinned);
+    buf = nullptr;
+    if (pinned) *pinned = nullptr;
+    cap = 0;
+    JCHK(c, hipMalloc(&buf, to));
+    if (pinned) JCHK(c, hipHostMalloc(pinned, to, hipHostMallocDefault));
+    cap = to;
     return PSN_LK_OK;
 }
 
 namespace jent = psn::jent;
 
-// Bytes of a workgroup's subsequences are staged in LDS up to this subsequence
-// size (256 subsequences + tables + states stay under 64 KiB); larger ones are
-// read from global memory.
-#ifndef PSN_JPEG_STAGE_MAX_SUB
-#define PSN_JPEG_STAGE_MAX_SUB 128
-#endif
-
-bool valid_entropy_request(int mode, int sub) {
-    return mode >= 0 && mode <= 2 && (sub == 0 || (sub >= jent::kMinSub && sub <= jent::kMaxSub && sub % 4 == 0));
-}
-
-// The planner: the parallel path is legal for a plain stream without restart
-// intervals, and it is the planner's choice wherever it is legal.
-void plan_entropy(const Parsed &P, int mode, int sub, psn_jpeg_plan &pl) {
-    memset(&pl, 0, sizeof pl);
-    pl.segments = P.a.nseg;
-    pl.plain = P.plain ? 1 : 0;
-    pl.entropy_bytes = P.a.data_len;
-    const bool legal = P.a.ri == 0 && P.plain && P.a.data_len > 0;
-    pl.path = mode != 1 && legal ? PSN_JPEG_PATH_PARALLEL : PSN_JPEG_PATH_SERIAL;
-    if (pl.path == PSN_JPEG_PATH_PARALLEL) {
-        pl.sub_bytes = sub ? sub : PSN_JPEG_DEFAULT_SUB_BYTES;
-        pl.subsequences = (P.a.data_len + pl.sub_bytes - 1) / pl.sub_bytes;
-        pl.sequences = (pl.subsequences + jent::kSeqLen - 1) / jent::kSeqLen;
-    }
-}
-
-// The scan's block layout as the symbol step's sinks address it.
-void entropy_geometry(const Parsed &P, jent::Geo &G, int &nb0, int &bpm) {
-    const psn::JpegArgs &a = P.a;
-    memset(&G, 0, sizeof G);
-    G.nc = a.nc;
-    G.mcux = a.mcux;
-    G.nblocks = a.nblocks;
-    for (int c = 0; c < a.nc; c++) {
-        G.c[c].h = a.nc == 1 ? 1 : a.c[c].h;
-        G.c[c].v = a.nc == 1 ? 1 : a.c[c].v;
-        G.c[c].bw = a.c[c].bw;
-        G.c[c].blk0 = a.c[c].blk0;
-    }
-    nb0 = G.c[0].h * G.c[0].v;
-    bpm = a.nc == 1 ? 1 : nb0 + a.nc - 1;  // chroma is 1x1 (parse())
-    G.total = a.nmcu * bpm;
-}
-
-// psn_jpeg_entropy_model's decode: the kernels' passes, one after the other.
-void model_decode(const Parsed &P, const uint8_t *ent, const psn_jpeg_plan &pl, int16_t *coef, psn_jpeg_stats &S) {
-    jent::Geo G;
-    int nb0, bpm;
-    entropy_geometry(P, G, nb0, bpm);
-    std::vector<psn::HuffDev> dc(psn::kJpegMaxComp), ac(psn::kJpegMaxComp);
-    for (int c = 0; c < P.a.nc; c++) {
-        dc[c] = P.tab.dc[P.a.c[c].td];
-        ac[c] = P.tab.ac[P.a.c[c].ta];
-    }
-    const jent::Tabs T{dc.data(), ac.data(), nb0, bpm};
-    const jent::HostBytes src{ent, P.a.data_len};
-    const long long total = G.total;
-    const unsigned long long kNoEnd = ~0ULL >> 16, kStart = jent::pack(0, 0, 0);
-    memset(coef, 0, (size_t)G.nblocks * 64 * sizeof(int16_t));
-    if (pl.path == PSN_JPEG_PATH_SERIAL) {
-        jent::EmitSink sink(G, T, coef, jent::kNaturalHost, 0);
-        jent::run(src, T, kStart, kNoEnd, (total + 1) * 64, sink);
-        S.blocks = (int)std::min(sink.g, total);
-    } else {
-        const int nsub = pl.subsequences, nseq = pl.sequences, K = jent::kSeqLen;
-        const long long subbits = 8LL * pl.sub_bytes;
-        std::vector<unsigned long long> st((size_t)nsub);
-        std::vector<unsigned> cnt((size_t)nsub);
-        auto sub = [&](long long i, unsigned long long from, unsigned &blocks) {
-            jent::CountSink cs;
-            const unsigned long long e = jent::run(src, T, from, (unsigned long long)((i + 1) * subbits), subbits + 1, cs);
-            blocks = cs.blocks;
-            return e;
-        };
-        // jpeg_sync_kernel: every thread of a round sees the previous round's exit states
-        for (int q = 0; q < nseq; q++) {
-            const long long i0 = (long long)q * K;
-            const int n = (int)std::min<long long>(K, nsub - i0);
-            std::vector<unsigned long long> entry((size_t)n), ex((size_t)n);
-            for (int t = 0; t < n; t++) {
-                entry[t] = i0 + t ? jent::cold_state(src, (i0 + t) * pl.sub_bytes) : kStart;
-                ex[t] = sub(i0 + t, entry[t], cnt[i0 + t]);
-            }
-            int rounds = 1;
-            for (int r = 1; r < K; r++) {
-                const std::vector<unsigned long long> prev = ex;
-                bool changed = false;
-                for (int t = 1; t < n; t++)
-                    if (prev[t - 1] != entry[t]) {
-                        entry[t] = prev[t - 1];
-                        const unsigned long long e = sub(i0 + t, entry[t], cnt[i0 + t]);
-                        changed |= e != ex[t];
-                        ex[t] = e;
-                    }
-                rounds++;
-                if (!changed) break;
-            }
-            std::copy(ex.begin(), ex.end(), st.begin() + i0);
-            S.sync_rounds = std::max(S.sync_rounds, rounds);
-        }
-        // jpeg_chain_kernel
-        unsigned long long carry = kStart;
-        for (int c0 = 0; c0 < nseq; c0 += jent::kChainLen) {
-            const int npass = std::min(jent::kChainLen, nseq - c0);
-            std::vector<unsigned long long> sx((size_t)npass), walked((size_t)npass, ~0ULL);
-            auto last_of = [&](int j) { return std::min<long long>((long long)(j + 1) * K, nsub) - 1; };
-            for (int t = 0; t < npass; t++) sx[t] = st[last_of(c0 + t)];
-            for (int r = 0; r < npass; r++) {
-                const std::vector<unsigned long long> prev = sx;
-                bool changed = false;
-                for (int t = 0; t < npass; t++) {
-                    const int j = c0 + t;
-                    const unsigned long long entry = t ? prev[t - 1] : carry;
-                    if (j == 0 || entry == walked[t]) continue;
-                    unsigned long long cur = entry;
-                    bool met = false;
-                    for (long long i = (long long)j * K; i <= last_of(j) && !met; i++) {
-                        unsigned blocks;
-                        cur = sub(i, cur, blocks);
-                        met = cur == st[i];
-                        st[i] = cur;
-                        cnt[i] = blocks;
-                    }
-                    if (!met && cur != sx[t]) {
-                        sx[t] = cur;
-                        changed = true;
-                    }
-                    walked[t] = entry;
-                }
-                S.chain_rounds++;
-                if (!changed) break;
-            }
-            carry = sx[npass - 1];
-        }
-        // prefix sum, jpeg_emit_kernel
-        long long g0 = 0;
-        for (long long i = 0; i < nsub; i++) {
-            const bool last = i == nsub - 1;
-            jent::EmitSink sink(G, T, coef, jent::kNaturalHost, g0);
-            const long long bound = subbits + 1 + (last ? (total - std::min(g0, total) + 1) * 64 : 0);
-            jent::run(src, T, i ? st[i - 1] : kStart, last ? kNoEnd : (unsigned long long)((i + 1) * subbits), bound, sink);
-            if (last) S.blocks = (int)std::min(sink.g, total);
-            g0 += cnt[i];
-        }
-    }
-    // jpeg_dc_kernel: the serial kernel's last_dc[ci] += diff; blk[0] = (int16_t)last_dc[ci]
-    for (int c = 0; c < P.a.nc; c++) {
-        const long long n = (long long)P.a.nmcu * G.c[c].h * G.c[c].v;
-        unsigned last_dc = 0;
-        for (long long e = 0; e < n; e++) {
-            int16_t &d0 = coef[jent::dc_block(G, c, e) * 64];
-            last_dc += (unsigned)(int)d0;
-            d0 = (int16_t)(int)last_dc;
-        }
-    }
-}
-
 }  // namespace
 
 extern "C" {
-
-int psn_jpeg_info(const uint8_t *data, size_t len, int *w, int *h, int *comps) {
-    if (!data || !w || !h) return PSN_LK_ERR_ARG;
-    Parsed P;
-    std::string why;
-    const int rc = parse(data, len, P, why);
-    if (rc) return rc;
-    *w = P.a.W;
-    *h = P.a.H;
-    if (comps) *comps = P.a.nc;
-    return PSN_LK_OK;
-}
 
 int psn_jpeg_create(int device, psn_jpeg_ctx **out) {
     if (!out) return PSN_LK_ERR_ARG;
@@ -990,17 +634,18 @@ int psn_jpeg_set_stream(psn_jpeg_ctx *c, void *s) {
     return PSN_LK_OK;
 }
 
-#define JCHK(c, e)                                                                                      \
-    do {                                                                                                \
-        hipError_t e_ = (e);                                                                            \
-        if (e_ != hipSuccess) return jerr((c), PSN_LK_ERR_HIP, "%s: %s", #e, hipGetErrorString(e_));   \
-    } while (0)
+// Bytes of a workgroup's subsequences are staged in LDS up to this subsequence
+// size (256 subsequences + tables + states stay under 64 KiB); larger ones are
+// read from global memory.
+#ifndef PSN_JPEG_STAGE_MAX_SUB
+#define PSN_JPEG_STAGE_MAX_SUB 128
+#endif
 
 int psn_jpeg_decode_device(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uint8_t *d_bgr, int stride) {
     if (!c || !data || !d_bgr) return PSN_LK_ERR_ARG;
-    Parsed P;
+    psn::Parsed P;
     std::string why;
-    int rc = parse(data, len, P, why);
+    int rc = psn::parse(data, len, P, why);
     if (rc) return jerr(c, rc, "%s", why.c_str());
     psn::JpegArgs &a = P.a;
     if (stride < 3 * a.W) return jerr(c, PSN_LK_ERR_ARG, "stride %d < 3 * width %d", stride, a.W);
@@ -1012,30 +657,10 @@ int psn_jpeg_decode_device(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uin
         JCHK(c, hipEventSynchronize(c->blob_free));
         c->blob_pending = false;
     }
-    if (c->blob_cap < blob) {
-        JCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_blob) (void)hipFree(c->d_blob);
-        if (c->h_blob) (void)hipHostFree(c->h_blob);
-        c->d_blob = c->h_blob = nullptr;
-        c->blob_cap = 0;
-        const size_t cap = blob + blob / 2;
-        JCHK(c, hipMalloc(&c->d_blob, cap));
-        JCHK(c, hipHostMalloc(&c->h_blob, cap, hipHostMallocDefault));
-        c->blob_cap = cap;
-    }
+    if ((rc = grow(c, c->d_blob, c->blob_cap, blob, blob + blob / 2, &c->h_blob))) return rc;
     const size_t coef = (size_t)a.nblocks * 64 * sizeof(int16_t), planes = (size_t)a.nblocks * 64;
-    if (c->coef_cap < coef || c->planes_cap < planes) {
-        JCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_coef) (void)hipFree(c->d_coef);
-        if (c->d_planes) (void)hipFree(c->d_planes);
-        c->d_coef = nullptr;
-        c->d_planes = nullptr;
-        c->coef_cap = c->planes_cap = 0;
-        JCHK(c, hipMalloc(&c->d_coef, coef));
-        JCHK(c, hipMalloc(&c->d_planes, planes));
-        c->coef_cap = coef;
-        c->planes_cap = planes;
-    }
+    if ((rc = grow(c, c->d_coef, c->coef_cap, coef, coef))) return rc;
+    if ((rc = grow(c, c->d_planes, c->planes_cap, planes, planes))) return rc;
     memcpy(c->h_blob, &P.tab, sizeof(psn::Tables));
     memcpy(c->h_blob + off_seg, P.seg.data(), 4 * P.seg.size());
     memcpy(c->h_blob + off_data, data + P.ent0, (size_t)a.data_len);
@@ -1051,7 +676,7 @@ int psn_jpeg_decode_device(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uin
     a.out = d_bgr;
     a.out_stride = stride;
     psn_jpeg_plan pl;
-    plan_entropy(P, c->ent_mode, c->ent_sub, pl);
+    psn::plan_entropy(P, c->ent_mode, c->ent_sub, pl);
     c->last = psn_jpeg_stats{pl.path, pl.segments, pl.sub_bytes, pl.subsequences, pl.sequences, 0, 0, 0};
     c->decoded = true;
     c->last_nblocks = a.nblocks;
@@ -1060,14 +685,7 @@ int psn_jpeg_decode_device(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uin
         auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
         const size_t off_st = up16(sizeof(psn::DevStats)), off_cnt = off_st + up16(8 * nsub), off_pre = off_cnt + up16(4 * nsub),
                      off_rounds = off_pre + up16(4 * nsub), par = off_rounds + up16(4 * nseq);
-        if (c->par_cap < par) {
-            JCHK(c, hipStreamSynchronize(c->stream));
-            if (c->d_par) (void)hipFree(c->d_par);
-            c->d_par = nullptr;
-            c->par_cap = 0;
-            JCHK(c, hipMalloc(&c->d_par, par + par / 2));
-            c->par_cap = par + par / 2;
-        }
+        if ((rc = grow(c, c->d_par, c->par_cap, par, par + par / 2))) return rc;
         psn::EntArgs e{};
         e.tab = a.tab;
         e.data = a.data;
@@ -1076,7 +694,7 @@ int psn_jpeg_decode_device(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uin
         e.nsub = pl.subsequences;
         e.nseq = pl.sequences;
         e.stage = pl.sub_bytes <= PSN_JPEG_STAGE_MAX_SUB ? 1 : 0;
-        entropy_geometry(P, e.geo, e.nb0, e.bpm);
+        psn::entropy_geometry(P, e.geo, e.nb0, e.bpm);
         e.nmcu = a.nmcu;
         for (int i = 0; i < a.nc; i++) {
             e.td[i] = a.c[i].td;
@@ -1118,14 +736,7 @@ int psn_jpeg_decode(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uint8_t *b
     if (stride < 3 * w) return jerr(c, PSN_LK_ERR_ARG, "stride %d < 3 * width %d", stride, w);
     JCHK(c, hipSetDevice(c->device));
     const size_t need = (size_t)w * 3 * h;
-    if (c->out_cap < need) {
-        JCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_out) (void)hipFree(c->d_out);
-        c->d_out = nullptr;
-        c->out_cap = 0;
-        JCHK(c, hipMalloc(&c->d_out, need));
-        c->out_cap = need;
-    }
+    if ((rc = grow(c, c->d_out, c->out_cap, need, need))) return rc;
     rc = psn_jpeg_decode_device(c, data, len, c->d_out, 3 * w);
     if (rc) return rc;
     JCHK(c, hipMemcpy2DAsync(bgr, stride, c->d_out, 3 * (size_t)w, 3 * (size_t)w, h, hipMemcpyDeviceToHost, c->stream));
@@ -1133,19 +744,9 @@ int psn_jpeg_decode(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uint8_t *b
     return PSN_LK_OK;
 }
 
-int psn_jpeg_entropy_plan(const uint8_t *data, size_t len, psn_jpeg_plan *out) {
-    if (!data || !out) return PSN_LK_ERR_ARG;
-    Parsed P;
-    std::string why;
-    const int rc = parse(data, len, P, why);
-    if (rc) return rc;
-    plan_entropy(P, 0, 0, *out);
-    return PSN_LK_OK;
-}
-
 int psn_jpeg_debug_set_entropy(psn_jpeg_ctx *c, int mode, int sub_bytes) {
     if (!c) return PSN_LK_ERR_ARG;
-    if (!valid_entropy_request(mode, sub_bytes))
+    if (!psn::valid_entropy_request(mode, sub_bytes))
         return jerr(c, PSN_LK_ERR_ARG, "entropy mode %d (0..2), sub_bytes %d (0 or a multiple of 4 in [4, 1024])", mode, sub_bytes);
     c->ent_mode = mode;
     c->ent_sub = sub_bytes;
@@ -1176,22 +777,6 @@ int psn_jpeg_last_stats(psn_jpeg_ctx *c, psn_jpeg_stats *out) {
         out->chain_rounds = d.chain_rounds;
         out->blocks = d.blocks;
     }
-    return PSN_LK_OK;
-}
-
-int psn_jpeg_entropy_model(const uint8_t *data, size_t len, int mode, int sub_bytes, int16_t *coef, psn_jpeg_stats *stats) {
-    if (!data || !stats || !valid_entropy_request(mode, sub_bytes)) return PSN_LK_ERR_ARG;
-    Parsed P;
-    std::string why;
-    const int rc = parse(data, len, P, why);
-    if (rc) return rc;
-    if (P.a.ri != 0 || !P.plain) return PSN_LK_ERR_UNSUPPORTED;
-    psn_jpeg_plan pl;
-    plan_entropy(P, mode, sub_bytes, pl);
-    *stats = psn_jpeg_stats{pl.path, pl.segments, pl.sub_bytes, pl.subsequences, pl.sequences, 0, 0, P.a.nblocks};
-    if (!coef) return PSN_LK_OK;
-    stats->blocks = 0;
-    model_decode(P, data + P.ent0, pl, coef, *stats);
     return PSN_LK_OK;
 }
 

@@ -1,7 +1,8 @@
 // One symbol of the baseline-JPEG entropy decode, written once for the host and
-// the device: the CPU model (psn_jpeg_entropy_model) and the parallel kernels of
-// psn_jpeg.hip (jpeg_sync_kernel, jpeg_chain_kernel, jpeg_emit_kernel) run these
-// functions, so a state the model reaches is the state a kernel reaches.
+// the device: the CPU model (psn_jpeg_entropy_model, psn_jpeg_model.cpp) and the
+// parallel kernels of psn_jpeg.hip (jpeg_sync_kernel, jpeg_chain_kernel,
+// jpeg_emit_kernel) run these functions, so a state the model reaches is the
+// state a kernel reaches.
 //
 // They read a *plain* stream: inside the entropy bytes every 0xFF is followed by
 // 0x00 and the last byte is not 0xFF -- no fill bytes, no embedded marker. A 0x00
@@ -54,13 +55,9 @@ static __constant__ uint8_t kNaturalDev[64 + 16] = PSN_JENT_NATURAL_INIT;  // th
 #endif
 static const uint8_t kNaturalHost[64 + 16] = PSN_JENT_NATURAL_INIT;
 
-PSN_JENT_HD inline int popc64(uint64_t x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __popcll(x);
-#else
-    return __builtin_popcountll(x);
-#endif
-}
+// The compiler builtin for host and device: HIP's __popcll wraps the same builtin,
+// and a unit that includes no HIP header has no __popcll when it is built as HIP.
+PSN_JENT_HD inline int popc64(uint64_t x) { return __builtin_popcountll(x); }
 
 PSN_JENT_HD inline uint64_t pack(uint64_t pos, int b, int zz) { return (pos << 16) | ((uint64_t)b << 8) | (uint64_t)zz; }
 PSN_JENT_HD inline uint64_t state_pos(uint64_t s) { return s >> 16; }
@@ -68,8 +65,9 @@ PSN_JENT_HD inline int state_b(uint64_t s) { return (int)((s >> 8) & 255); }
 PSN_JENT_HD inline int state_zz(uint64_t s) { return (int)(s & 255); }
 
 // The scan's tables by component and the MCU's block layout: blocks 0..nb0-1 of an
-// MCU are component 0's, each later block is one further component's (parse()
-// admits 1x1 chroma only; a one-component scan has one block per MCU).
+// MCU are component 0's, each later block is one further component's (parse() of
+// psn_jpeg_parse.cpp admits 1x1 chroma only; a one-component scan has one block
+// per MCU).
 struct Tabs {
     const HuffDev *dc, *ac;   // [component]
     int nb0, bpm;             // component 0's blocks per MCU, all blocks per MCU

@@ -1,0 +1,90 @@
+// The host side of the JPEG ingest that touches no device: the marker parser
+// (the one place in the library that reads bytes straight from a camera), the
+// Huffman table builder and the entropy planner, with the argument structs the
+// kernels of psn_jpeg.hip take. Plain C++17, no HIP header: psn_jpeg_parse.cpp
+// and psn_jpeg_model.cpp build with a host compiler alone, which is how
+// tests/test_jpeg_host.py puts them under the sanitizers.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "psn_jpeg.h"
+#include "psn_jpeg_entropy.h"  // HuffDev, the symbol step of the parallel path
+#include "psn_lk.h"
+
+namespace psn {
+
+constexpr int kJpegMaxComp = 3;
+
+struct Tables {             // device copy per frame
+    uint16_t qt[4][64];     // natural order
+    HuffDev dc[4], ac[4];
+};
+
+struct CompGeo {
+    int h, v, tq, td, ta;   // sampling factors, table selectors
+    int bw, bh;             // blocks across / down (plane = bw*8 x bh*8)
+    int dw, dh;             // downsampled size (edges of the fancy upsampler)
+    int blk0;               // first coefficient block
+    int plane0;             // byte offset of the plane
+};
+
+struct JpegArgs {
+    int W, H, nc, hmax, vmax, mcux, nmcu, ri, nseg, data_len;
+    CompGeo c[kJpegMaxComp];
+    const Tables *tab;
+    const int *seg;          // byte offset of each segment's first entropy byte
+    const uint8_t *data;     // entropy-coded bytes
+    int16_t *coef;           // [blocks][64], natural order
+    uint8_t *planes;
+    uint8_t *out;
+    int out_stride;
+    int nblocks;
+};
+
+// A parsed frame: tables, geometry, entropy segments.
+struct Parsed {
+    Tables tab;
+    JpegArgs a{};
+    std::vector<int> seg;
+    size_t ent0 = 0, ent1 = 0;  // entropy bytes [ent0, ent1) of the file
+    // every 0xFF in [ent0, ent1) is followed by 0x00 and the last byte is not 0xFF:
+    // no fill bytes, no embedded marker (psn_jpeg_entropy.h reads such streams)
+    bool plain = true;
+    // per Huffman slot (class tc, index th): 0 never defined, 1 valid, -1 the last
+    // definition is one jpeg_make_d_derived_tbl rejects -- an error only for a table
+    // the scan uses (libjpeg builds the derived tables of the scan's components)
+    int hstate[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+};
+
+// Calls between the units of the library, not part of its interface.
+#pragma GCC visibility push(hidden)
+
+// The headers and the entropy segments of the `n` bytes at `d`; reads nothing
+// outside them. PSN_LK_OK, or PSN_LK_ERR_ARG / PSN_LK_ERR_UNSUPPORTED with the
+// reason in `why`.
+int parse(const uint8_t *d, size_t n, Parsed &P, std::string &why);
+
+// jdhuff.c jpeg_make_d_derived_tbl: false for a table libjpeg rejects with
+// JERR_BAD_HUFF_TABLE -- more codes of a length than fit after the shorter ones
+// (the canonical code would overflow its length; the all-ones code is not
+// allowed), or a DC symbol above 15. Checked before any table entry is written.
+bool build_huff(const uint8_t *bits, const uint8_t *vals, int nvals, bool dc, HuffDev &h);
+
+// psn_jpeg_debug_set_entropy's and psn_jpeg_entropy_model's mode and sub_bytes.
+bool valid_entropy_request(int mode, int sub);
+
+// The planner: the parallel path is legal for a plain stream without restart
+// intervals, and it is the planner's choice wherever it is legal.
+void plan_entropy(const Parsed &P, int mode, int sub, psn_jpeg_plan &pl);
+
+// The scan's block layout as the symbol step's sinks address it.
+void entropy_geometry(const Parsed &P, jent::Geo &G, int &nb0, int &bpm);
+
+#pragma GCC visibility pop
+
+}  // namespace psn
