@@ -111,6 +111,69 @@ int psn_jpeg_debug_set_entropy(psn_jpeg_ctx *ctx, int mode, int sub_bytes);
  * otherwise, or when nothing has been decoded. */
 int psn_jpeg_debug_read_coefficients(psn_jpeg_ctx *ctx, int16_t *out, size_t count);
 
+/* ---- batches ------------------------------------------------------------- */
+
+/* The frames of one frame-set (one file per camera) decoded in one device pass:
+ * one pinned staging blob and one H2D copy for all items, one memset, and one
+ * fixed number of kernel launches whatever n -- every kernel has a batch entry
+ * whose grid carries the item index and whose workgroups past an item's own
+ * extent return at once. Items may differ in size, components, subsampling and
+ * entropy path; every item's output is that of psn_jpeg_decode_device alone. */
+#define PSN_JPEG_MAX_BATCH 64
+typedef struct psn_jpeg_item {
+    const uint8_t *data;
+    size_t len;
+    uint8_t *d_bgr; /* device memory: height rows of width*3 bytes, `stride` apart */
+    int stride;
+} psn_jpeg_item;
+
+/* All or nothing: n in [1, PSN_JPEG_MAX_BATCH], the pointers, every item's
+ * headers and its stride are checked before anything is enqueued; the first bad
+ * item's error is returned with "item <index>" in psn_jpeg_last_error, and the
+ * context is left as it was. Asynchronous on the decoder's stream; the files'
+ * bytes are copied before the call returns. psn_jpeg_debug_set_entropy applies
+ * to every item. Afterwards psn_jpeg_last_stats and
+ * psn_jpeg_debug_read_coefficients speak of the batch's last item. */
+int psn_jpeg_decode_batch_device(psn_jpeg_ctx *ctx, const psn_jpeg_item *items, int n);
+/* psn_jpeg_last_stats / psn_jpeg_debug_read_coefficients of item `item` of the
+ * context's last batch (both wait for the decoder's stream); PSN_LK_ERR_ARG when
+ * the last decode was not a batch or had no such item. */
+int psn_jpeg_batch_stats(psn_jpeg_ctx *ctx, int item, psn_jpeg_stats *out);
+int psn_jpeg_debug_read_batch_coefficients(psn_jpeg_ctx *ctx, int item, int16_t *out, size_t count);
+
+/* Where a batch puts each item (host only, no device work): byte offsets into
+ * the staging blob, the parallel path's scratch, the coefficients and the
+ * planes. Every offset is a multiple of 16; an item's entropy bytes are followed
+ * by 16 zeroed bytes of its own (bytes_size >= entropy_bytes + 16), which is
+ * what the kernels may read past the data. */
+typedef struct psn_jpeg_batch_item_layout {
+    int path;              /* PSN_JPEG_PATH_* */
+    int list_index;        /* position in the parallel / serial list */
+    size_t tables, segments, bytes;                 /* staging blob */
+    size_t segments_size, bytes_size;
+    size_t stats, states, counts, prefix, rounds;   /* scratch (states .. rounds: parallel items; else sizes 0) */
+    size_t states_size, counts_size, prefix_size, rounds_size;
+    size_t coef, coef_size;                          /* int16 [blocks][64] */
+    size_t planes, planes_size;
+} psn_jpeg_batch_item_layout;
+
+typedef struct psn_jpeg_batch_layout {
+    int n;
+    int bad_item;          /* on an error: the first bad item, -1 for the call's own arguments */
+    int n_parallel, n_serial;
+    int parallel[PSN_JPEG_MAX_BATCH], serial[PSN_JPEG_MAX_BATCH]; /* item indices, ascending */
+    /* the blob's tail: the kernels' two argument tables ([n] each) and the two lists */
+    size_t ent_args, jpeg_args, lists;
+    size_t blob_size, scratch_size, coef_size, planes_size;
+    /* grid maxima over the items (parallel items: sequences, components) */
+    int max_sequences, max_parallel_components, max_segment_groups /* ceil(segments / 64), serial items */;
+    int max_block_groups /* ceil(blocks / 256) */, max_width, max_height;
+    psn_jpeg_batch_item_layout item[PSN_JPEG_MAX_BATCH];
+} psn_jpeg_batch_layout;
+/* The planner at its defaults (psn_jpeg_entropy_plan per item). d_bgr is only
+ * checked for null. plans may be NULL. */
+int psn_jpeg_batch_plan(const psn_jpeg_item *items, int n, psn_jpeg_batch_layout *out, psn_jpeg_plan *plans);
+
 /* CPU model of the entropy decode (host only): the symbol step the kernels run
  * (csrc/psn_jpeg_entropy.h) with the kernels' rounds emulated sequentially.
  * coef receives the scan's [blocks][64] coefficients in natural order, DC

@@ -196,11 +196,24 @@ int psn_lk_push_frame_async(psn_lk_ctx *ctx, int slot, const uint8_t *host, int 
  * the ingest stream; `jpeg` is copied before the call returns. */
 int psn_lk_push_frame_jpeg(psn_lk_ctx *ctx, int slot, const uint8_t *jpeg, size_t len);
 
-/* Which entropy path the context's last psn_lk_push_frame_jpeg took and its
+/* n JPEG frames into n different slots at once (a frame-set's cameras): what
+ * psn_lk_push_frame_jpeg does per slot, with one batched decode
+ * (psn_jpeg_decode_batch_device: one upload, one launch per kernel for all
+ * frames) in place of n decodes in series; the pyramid builds stay one launch
+ * per slot. n in [1, PSN_JPEG_MAX_BATCH]. All or nothing: a repeated slot
+ * (PSN_LK_ERR_SLOT) or a frame that is not a JPEG of the source size is refused,
+ * with "item <index>" in psn_lk_last_error, before any slot is touched. */
+int psn_lk_push_frames_jpeg(psn_lk_ctx *ctx, const int *slots, const uint8_t *const *jpeg, const size_t *len, int n);
+
+/* Which entropy path the context's last psn_lk_push_frame_jpeg (the last frame
+ * of its last psn_lk_push_frames_jpeg) took and its
  * round counters (psn_jpeg_last_stats of the context's decoder; waits for the
  * ingest stream). PSN_LK_ERR_ARG before the first JPEG push. */
 struct psn_jpeg_stats;
 int psn_lk_jpeg_last_stats(psn_lk_ctx *ctx, struct psn_jpeg_stats *out);
+/* The same of frame `item` of the last psn_lk_push_frames_jpeg (psn_jpeg_batch_stats):
+ * PSN_LK_ERR_ARG when the context's last JPEG push was a single frame or had fewer frames. */
+int psn_lk_jpeg_batch_stats(psn_lk_ctx *ctx, int item, struct psn_jpeg_stats *out);
 
 /* Ingest overlap modes (default OFF: builds run on the context stream).
  * STREAM: psn_lk_push_frame* builds the pyramid on the context's internal

@@ -290,6 +290,9 @@ int psn_t2d_group_push_frame(psn_t2d_group *g, int cam, const uint8_t *frame, in
 int psn_t2d_group_push_frame_device(psn_t2d_group *g, int cam, const uint8_t *dev_frame, int stride, int channels);
 /* the camera's frame as a baseline JPEG file (decoded on the device, psn_lk_push_frame_jpeg) */
 int psn_t2d_group_push_frame_jpeg(psn_t2d_group *g, int cam, const uint8_t *jpeg, size_t len);
+/* every camera's frame t at once, one file per camera in camera order: one batched device decode
+ * (psn_lk_push_frames_jpeg) in place of one decode per camera; all or nothing */
+int psn_t2d_group_push_frames_jpeg(psn_t2d_group *g, const uint8_t *const *jpeg, const size_t *len);
 int psn_t2d_group_launch(psn_t2d_group *g, unsigned frame_idx, psn_t2d_detection *const *dets, const int *ndet,
                          int feature_mode, uint32_t seed);
 int psn_t2d_group_complete(psn_t2d_group *g, psn_t2d_detection *const *dets, const int *ndet,

@@ -112,6 +112,30 @@ class JpegStats(ctypes.Structure):
 
 
 JPEG_PATH_SERIAL, JPEG_PATH_PARALLEL = 0, 1
+JPEG_MAX_BATCH = 64  # PSN_JPEG_MAX_BATCH
+
+
+class JpegItem(ctypes.Structure):
+    """psn_jpeg_item (include/psn_jpeg.h)."""
+    _fields_ = [("data", ctypes.c_void_p), ("len", ctypes.c_size_t), ("d_bgr", ctypes.c_void_p), ("stride", ctypes.c_int)]
+
+
+class JpegBatchItemLayout(ctypes.Structure):
+    """psn_jpeg_batch_item_layout (include/psn_jpeg.h)."""
+    _fields_ = [("path", ctypes.c_int), ("list_index", ctypes.c_int)] + [(n, ctypes.c_size_t) for n in (
+        "tables", "segments", "bytes", "segments_size", "bytes_size", "stats", "states", "counts", "prefix", "rounds",
+        "states_size", "counts_size", "prefix_size", "rounds_size", "coef", "coef_size", "planes", "planes_size")]
+
+
+class JpegBatchLayout(ctypes.Structure):
+    """psn_jpeg_batch_layout (include/psn_jpeg.h)."""
+    _fields_ = ([(n, ctypes.c_int) for n in ("n", "bad_item", "n_parallel", "n_serial")]
+                + [("parallel", ctypes.c_int * JPEG_MAX_BATCH), ("serial", ctypes.c_int * JPEG_MAX_BATCH)]
+                + [(n, ctypes.c_size_t) for n in ("ent_args", "jpeg_args", "lists", "blob_size", "scratch_size",
+                                                   "coef_size", "planes_size")]
+                + [(n, ctypes.c_int) for n in ("max_sequences", "max_parallel_components", "max_segment_groups",
+                                               "max_block_groups", "max_width", "max_height")]
+                + [("item", JpegBatchItemLayout * JPEG_MAX_BATCH)])
 
 
 def struct_dict(s: ctypes.Structure) -> dict:
@@ -251,6 +275,15 @@ def load(path: str | None = None):
         L.psn_lk_jpeg_last_stats.argtypes = [vp, ctypes.POINTER(JpegStats)]
     if hasattr(L, "psn_jpeg_debug_read_coefficients"):
         L.psn_jpeg_debug_read_coefficients.argtypes = [vp, vp, ctypes.c_size_t]
+    if hasattr(L, "psn_jpeg_decode_batch_device"):
+        L.psn_jpeg_decode_batch_device.argtypes = [vp, ctypes.POINTER(JpegItem), ip]
+        L.psn_jpeg_batch_stats.argtypes = [vp, ip, ctypes.POINTER(JpegStats)]
+        L.psn_jpeg_debug_read_batch_coefficients.argtypes = [vp, ip, vp, ctypes.c_size_t]
+        L.psn_jpeg_batch_plan.argtypes = [ctypes.POINTER(JpegItem), ip, ctypes.POINTER(JpegBatchLayout),
+                                          ctypes.POINTER(JpegPlan)]
+        L.psn_lk_jpeg_batch_stats.argtypes = [vp, ip, ctypes.POINTER(JpegStats)]
+        L.psn_lk_push_frames_jpeg.argtypes = [vp, ctypes.POINTER(ip), ctypes.POINTER(vp),
+                                              ctypes.POINTER(ctypes.c_size_t), ip]
     L.psn_lk_debug_set_variant.argtypes = [vp, ip, ip]
     L.psn_lk_track.argtypes = [vp, ctypes.POINTER(LkQuery), ip, fp, fp, u8p, fp]
     L.psn_lk_track_device.argtypes = [vp, ctypes.POINTER(LkQuery), ip, vp, vp, vp, vp]

@@ -30,6 +30,11 @@
 //   K3     jpeg_color_kernel: one thread per pixel: fancy upsampling (jdsample.c
 //          h2v1 / h2v2, edges replicated at the downsampled size), YCbCr->RGB
 //          (jdcolor.c, SCALEBITS 16), BGR out
+//   batch  psn_jpeg_decode_batch_device: every kernel has a *_batch_kernel entry
+//          over the same body, the item index in the grid; one blob
+//          [per item: tables | segment offsets | entropy bytes + 16 zeroed bytes]
+//          [EntArgs table | JpegArgs table | parallel list | serial list], one
+//          H2D, one memset, one launch per kernel whatever the item count
 // Bit-identical to oracle/jpeg_oracle.c, which is pinned to libjpeg-turbo.
 //
 // This unit: the kernels with their device-only structs, the decoder context,
@@ -122,8 +127,12 @@ struct BitReader {
 
 __device__ __forceinline__ int extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
 
-__global__ __launch_bounds__(64) void jpeg_entropy_kernel(JpegArgs A) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+// Every kernel's body is a device function over its argument struct and the
+// indices a single-image launch reads from blockIdx: the single-image entry
+// passes its by-value argument and blockIdx, the batch entry (the end of the
+// namespace) an item's arguments from a device table and the item's own index.
+__device__ __forceinline__ void entropy_body(const JpegArgs &A, int group) {
+    const int s = group * blockDim.x + threadIdx.x;
     if (s >= A.nseg) return;
     const Tables &T = *A.tab;
     BitReader br;
@@ -163,32 +172,12 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(JpegArgs A) {
     }
 }
 
+__global__ __launch_bounds__(64) void jpeg_entropy_kernel(JpegArgs A) { entropy_body(A, blockIdx.x); }
+
 // ---------------------------------------------------------------- parallel path
 // Subsequence i owns the bits [i * 8S, (i + 1) * 8S) of the entropy bytes: its
 // thread decodes the symbols that start there, and its exit state is the state at
-// the first symbol boundary at or past its end.
-
-struct DevStats {           // written by the kernels, read by psn_jpeg_last_stats
-    int sync_rounds, chain_rounds, blocks, pad;
-};
-
-struct EntArgs {
-    const Tables *tab;
-    const uint8_t *data;     // entropy bytes (readable 16 bytes past len)
-    long long len;
-    int S;                   // subsequence bytes
-    int nsub, nseq;          // subsequences, sequences of jent::kSeqLen
-    int stage;               // 1: the workgroup's bytes are staged in LDS
-    int nb0, bpm, nmcu;
-    int td[kJpegMaxComp], ta[kJpegMaxComp];
-    jent::Geo geo;
-    unsigned long long *st;  // [nsub] exit state
-    unsigned *cnt;           // [nsub] blocks completed inside the subsequence
-    unsigned *pre;           // [nsub] exclusive prefix sum of cnt
-    int *seq_rounds;         // [nseq] rounds of jpeg_sync_kernel's workgroup
-    DevStats *stats;
-    int16_t *coef;
-};
+// the first symbol boundary at or past its end. (EntArgs, DevStats: psn_jpeg_parse.h.)
 
 struct LdsTabs {            // the scan's tables by component (lookups are divergent)
     HuffDev dc[kJpegMaxComp], ac[kJpegMaxComp];
@@ -223,28 +212,27 @@ struct DevBytes {
 };
 
 // Stage the bytes of the workgroup's kSeqLen subsequences (plus slack) as dwords.
-__device__ __forceinline__ DevBytes stage_bytes(const EntArgs &E, uint8_t *sb) {
+__device__ __forceinline__ DevBytes stage_bytes(const EntArgs &E, int seq, uint8_t *sb) {
     DevBytes src{sb, 0, 0, E.data, E.len};
     if (E.stage) {
-        src.w0 = (long long)blockIdx.x * jent::kSeqLen * E.S;
+        src.w0 = (long long)seq * jent::kSeqLen * E.S;
         src.w1 = min(src.w0 + (long long)jent::kSeqLen * E.S + kStageSlack, E.len);
-        const int nd = (int)((src.w1 - src.w0 + 3) / 4);  // the last dword may read past len: inside the blob's slack
+        const int nd = (int)((src.w1 - src.w0 + 3) / 4);  // the last dword may read past len: inside the item's own slack
         const uint32_t *s = (const uint32_t *)(E.data + src.w0);
         for (int k = threadIdx.x; k < nd; k += blockDim.x) ((uint32_t *)sb)[k] = s[k];
     }
     return src;
 }
 
-__global__ __launch_bounds__(256) void jpeg_sync_kernel(EntArgs E) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+__device__ __forceinline__ void sync_body(const EntArgs &E, int seq, uint8_t *smem) {
     LdsTabs &L = *(LdsTabs *)smem;
     unsigned long long *sx = (unsigned long long *)(smem + sizeof(LdsTabs));  // exit state per thread
     stage_tables(E, L);
-    const DevBytes src = stage_bytes(E, smem + sizeof(LdsTabs) + jent::kSeqLen * 8);
+    const DevBytes src = stage_bytes(E, seq, smem + sizeof(LdsTabs) + jent::kSeqLen * 8);
     __syncthreads();
     const jent::Tabs T{L.dc, L.ac, E.nb0, E.bpm};
     const int t = threadIdx.x;
-    const long long i = (long long)blockIdx.x * jent::kSeqLen + t;
+    const long long i = (long long)seq * jent::kSeqLen + t;
     const bool active = i < E.nsub;
     const long long subbits = 8LL * E.S;
     const unsigned long long end = (unsigned long long)((i + 1) * subbits);
@@ -281,7 +269,12 @@ __global__ __launch_bounds__(256) void jpeg_sync_kernel(EntArgs E) {
         E.st[i] = ex;
         E.cnt[i] = cnt;
     }
-    if (t == 0) E.seq_rounds[blockIdx.x] = rounds;
+    if (t == 0) E.seq_rounds[seq] = rounds;
+}
+
+__global__ __launch_bounds__(256) void jpeg_sync_kernel(EntArgs E) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    sync_body(E, blockIdx.x, smem);
 }
 
 // Inclusive scan over the workgroup (any multiple of 64 threads up to 1024);
@@ -305,7 +298,7 @@ __device__ __forceinline__ unsigned block_scan_incl(unsigned v, unsigned *ws, un
     return v + off;
 }
 
-__global__ __launch_bounds__(1024) void jpeg_chain_kernel(EntArgs E) {
+__device__ __forceinline__ void chain_body(const EntArgs &E) {
     __shared__ LdsTabs L;
     __shared__ unsigned long long sx[jent::kChainLen];  // last exit state of each sequence of the pass
     __shared__ unsigned ws[16];
@@ -375,15 +368,16 @@ __global__ __launch_bounds__(1024) void jpeg_chain_kernel(EntArgs E) {
     }
 }
 
-__global__ __launch_bounds__(256) void jpeg_emit_kernel(EntArgs E) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+__global__ __launch_bounds__(1024) void jpeg_chain_kernel(EntArgs E) { chain_body(E); }
+
+__device__ __forceinline__ void emit_body(const EntArgs &E, int seq, uint8_t *smem) {
     LdsTabs &L = *(LdsTabs *)smem;
     uint8_t *snat = smem + sizeof(LdsTabs);  // the natural-order table: a divergent lookup per coefficient
     stage_tables(E, L);
     if (threadIdx.x < 64 + 16) snat[threadIdx.x] = jent::kNaturalDev[threadIdx.x];
-    const DevBytes src = stage_bytes(E, smem + sizeof(LdsTabs) + kNaturalLds);
+    const DevBytes src = stage_bytes(E, seq, smem + sizeof(LdsTabs) + kNaturalLds);
     __syncthreads();
-    const long long i = (long long)blockIdx.x * jent::kSeqLen + threadIdx.x;
+    const long long i = (long long)seq * jent::kSeqLen + threadIdx.x;
     if (i >= E.nsub) return;
     const jent::Tabs T{L.dc, L.ac, E.nb0, E.bpm};
     const long long subbits = 8LL * E.S, total = E.geo.total;
@@ -398,9 +392,13 @@ __global__ __launch_bounds__(256) void jpeg_emit_kernel(EntArgs E) {
     if (last) E.stats->blocks = (int)min(sink.g, total);
 }
 
-__global__ __launch_bounds__(1024) void jpeg_dc_kernel(EntArgs E) {
+__global__ __launch_bounds__(256) void jpeg_emit_kernel(EntArgs E) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    emit_body(E, blockIdx.x, smem);
+}
+
+__device__ __forceinline__ void dc_body(const EntArgs &E, int ci) {
     __shared__ unsigned ws[16];
-    const int ci = blockIdx.x;
     const long long n = (long long)E.nmcu * E.geo.c[ci].h * E.geo.c[ci].v;
     unsigned last_dc = 0;  // the serial kernel's last_dc[ci], modulo 2^32
     for (long long base = 0; base < n; base += blockDim.x) {
@@ -414,6 +412,8 @@ __global__ __launch_bounds__(1024) void jpeg_dc_kernel(EntArgs E) {
         last_dc += tot;
     }
 }
+
+__global__ __launch_bounds__(1024) void jpeg_dc_kernel(EntArgs E) { dc_body(E, blockIdx.x); }
 
 __device__ __forceinline__ long long desc(long long x, int n) { return (x + (1LL << (n - 1))) >> n; }
 __device__ __forceinline__ uint8_t range_limit(long long v) {
@@ -453,8 +453,8 @@ __device__ __forceinline__ void idct8(const long long (&d)[8], long long (&o)[8]
     o[4] = t13 - a0;
 }
 
-__global__ __launch_bounds__(256) void jpeg_idct_kernel(JpegArgs A) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void idct_body(const JpegArgs &A, int group) {
+    const int b = group * blockDim.x + threadIdx.x;
     if (b >= A.nblocks) return;
     int ci = 0;
     while (ci + 1 < A.nc && b >= A.c[ci + 1].blk0) ci++;
@@ -485,6 +485,8 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(JpegArgs A) {
     }
 }
 
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(JpegArgs A) { idct_body(A, blockIdx.x); }
+
 // One fancy-upsampled chroma sample at full-resolution (x, y).
 __device__ __forceinline__ int chroma(const JpegArgs &A, const CompGeo &g, int x, int y) {
     const uint8_t *pl = A.planes + g.plane0;
@@ -510,8 +512,8 @@ __device__ __forceinline__ int chroma(const JpegArgs &A, const CompGeo &g, int x
 
 __device__ __forceinline__ uint8_t clamp255(int v) { return (uint8_t)min(max(v, 0), 255); }
 
-__global__ __launch_bounds__(256) void jpeg_color_kernel(JpegArgs A) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+__device__ __forceinline__ void color_body(const JpegArgs &A, int group, int y) {
+    const int x = group * blockDim.x + threadIdx.x;
     if (x >= A.W) return;
     const CompGeo &gy = A.c[0];
     const int Y = A.planes[gy.plane0 + (size_t)y * (gy.bw * 8) + x];
@@ -527,6 +529,59 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(JpegArgs A) {
     o[0] = clamp255(Y + b);
     o[1] = clamp255(Y + (gsum >> 16));
     o[2] = clamp255(Y + r);
+}
+
+__global__ __launch_bounds__(256) void jpeg_color_kernel(JpegArgs A) { color_body(A, blockIdx.x, blockIdx.y); }
+
+// ---------------------------------------------------------------- batch entries
+// psn_jpeg_decode_batch_device: one launch per kernel for all items. The item is
+// blockIdx.y (blockIdx.z for the colour kernel, whose y is the row); the entropy
+// kernels take it through the index list of their path. The item's arguments are
+// read from a device table -- the index is uniform, so these are scalar loads, as
+// the single-image entries' kernel-argument loads are. The grid is the maximum
+// over the items: a workgroup past its own item's extent returns whole, before any
+// barrier of the body.
+
+__global__ __launch_bounds__(64) void jpeg_entropy_batch_kernel(const JpegArgs *__restrict__ tab, const int *__restrict__ list) {
+    const JpegArgs &A = tab[list[blockIdx.y]];
+    if ((int)blockIdx.x >= (A.nseg + 63) / 64) return;
+    entropy_body(A, blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void jpeg_sync_batch_kernel(const EntArgs *__restrict__ tab, const int *__restrict__ list) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const EntArgs &E = tab[list[blockIdx.y]];
+    if ((int)blockIdx.x >= E.nseq) return;
+    sync_body(E, blockIdx.x, smem);
+}
+
+__global__ __launch_bounds__(1024) void jpeg_chain_batch_kernel(const EntArgs *__restrict__ tab, const int *__restrict__ list) {
+    chain_body(tab[list[blockIdx.y]]);  // one workgroup per item
+}
+
+__global__ __launch_bounds__(256) void jpeg_emit_batch_kernel(const EntArgs *__restrict__ tab, const int *__restrict__ list) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const EntArgs &E = tab[list[blockIdx.y]];
+    if ((int)blockIdx.x >= E.nseq) return;
+    emit_body(E, blockIdx.x, smem);
+}
+
+__global__ __launch_bounds__(1024) void jpeg_dc_batch_kernel(const EntArgs *__restrict__ tab, const int *__restrict__ list) {
+    const EntArgs &E = tab[list[blockIdx.y]];
+    if ((int)blockIdx.x >= E.geo.nc) return;
+    dc_body(E, blockIdx.x);  // one workgroup per item and component
+}
+
+__global__ __launch_bounds__(256) void jpeg_idct_batch_kernel(const JpegArgs *__restrict__ tab) {
+    const JpegArgs &A = tab[blockIdx.y];
+    if ((int)blockIdx.x >= (A.nblocks + 255) / 256) return;
+    idct_body(A, blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void jpeg_color_batch_kernel(const JpegArgs *__restrict__ tab) {
+    const JpegArgs &A = tab[blockIdx.z];
+    if ((int)blockIdx.x >= (A.W + 255) / 256 || (int)blockIdx.y >= A.H) return;
+    color_body(A, blockIdx.x, blockIdx.y);
 }
 
 }  // namespace
@@ -551,6 +606,13 @@ struct psn_jpeg_ctx {
     psn_jpeg_stats last{};          // the last decode (host part; the kernels' counters are in d_par)
     bool decoded = false;
     int last_nblocks = 0;           // coefficient blocks of the last decode (psn_jpeg_debug_read_coefficients)
+    size_t last_stats_off = 0, last_coef_off = 0;  // its DevStats in d_par, its coefficients in d_coef (bytes)
+    struct BatchItem {              // psn_jpeg_batch_stats, psn_jpeg_debug_read_batch_coefficients
+        psn_jpeg_stats st;
+        int nblocks;
+        size_t stats_off, coef_off;
+    };
+    std::vector<BatchItem> batch;   // the items of the last decode when it was a batch; else empty
     std::string err;
 };
 
@@ -634,13 +696,6 @@ int psn_jpeg_set_stream(psn_jpeg_ctx *c, void *s) {
     return PSN_LK_OK;
 }
 
-// Bytes of a workgroup's subsequences are staged in LDS up to this subsequence
-// size (256 subsequences + tables + states stay under 64 KiB); larger ones are
-// read from global memory.
-#ifndef PSN_JPEG_STAGE_MAX_SUB
-#define PSN_JPEG_STAGE_MAX_SUB 128
-#endif
-
 int psn_jpeg_decode_device(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uint8_t *d_bgr, int stride) {
     if (!c || !data || !d_bgr) return PSN_LK_ERR_ARG;
     psn::Parsed P;
@@ -680,6 +735,8 @@ int psn_jpeg_decode_device(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uin
     c->last = psn_jpeg_stats{pl.path, pl.segments, pl.sub_bytes, pl.subsequences, pl.sequences, 0, 0, 0};
     c->decoded = true;
     c->last_nblocks = a.nblocks;
+    c->last_stats_off = c->last_coef_off = 0;
+    c->batch.clear();
     if (pl.path == PSN_JPEG_PATH_PARALLEL) {
         const size_t nsub = (size_t)pl.subsequences, nseq = (size_t)pl.sequences;
         auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
@@ -744,6 +801,110 @@ int psn_jpeg_decode(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uint8_t *b
     return PSN_LK_OK;
 }
 
+int psn_jpeg_decode_batch_device(psn_jpeg_ctx *c, const psn_jpeg_item *items, int n) {
+    if (!c) return PSN_LK_ERR_ARG;
+    psn::Batch B;
+    std::string why;
+    int rc = psn::plan_batch(items, n, c->ent_mode, c->ent_sub, B, why);  // every item, before anything is enqueued
+    if (rc) return jerr(c, rc, "%s", why.c_str());
+    const psn_jpeg_batch_layout &L = B.L;
+    JCHK(c, hipSetDevice(c->device));
+    if (c->blob_pending) {  // the staging blob is reused: the previous decode's H2D must be done
+        JCHK(c, hipEventSynchronize(c->blob_free));
+        c->blob_pending = false;
+    }
+    if ((rc = grow(c, c->d_blob, c->blob_cap, L.blob_size, L.blob_size + L.blob_size / 2, &c->h_blob))) return rc;
+    if ((rc = grow(c, c->d_coef, c->coef_cap, L.coef_size, L.coef_size))) return rc;
+    if ((rc = grow(c, c->d_planes, c->planes_cap, L.planes_size, L.planes_size))) return rc;
+    if ((rc = grow(c, c->d_par, c->par_cap, L.scratch_size, L.scratch_size + L.scratch_size / 2))) return rc;
+    psn::EntArgs *he = (psn::EntArgs *)(c->h_blob + L.ent_args);
+    psn::JpegArgs *ha = (psn::JpegArgs *)(c->h_blob + L.jpeg_args);
+    int *hl = (int *)(c->h_blob + L.lists);
+    std::vector<psn_jpeg_ctx::BatchItem> rec((size_t)n);
+    int sub = 0;  // the parallel items' subsequence size: one per context
+    for (int i = 0; i < n; i++) {
+        const psn::Parsed &P = B.P[(size_t)i];
+        const psn_jpeg_batch_item_layout &it = L.item[i];
+        const psn_jpeg_plan &pl = B.plans[(size_t)i];
+        memcpy(c->h_blob + it.tables, &P.tab, sizeof(psn::Tables));
+        memcpy(c->h_blob + it.segments, P.seg.data(), 4 * P.seg.size());
+        memcpy(c->h_blob + it.bytes, items[i].data + P.ent0, (size_t)P.a.data_len);
+        memset(c->h_blob + it.bytes + P.a.data_len, 0, it.bytes_size - (size_t)P.a.data_len);  // the item's slack
+        psn::batch_args(B, i, items[i], c->d_blob, c->d_par, (uint8_t *)c->d_coef, c->d_planes, ha[i], he[i]);
+        rec[(size_t)i] = {psn_jpeg_stats{pl.path, pl.segments, pl.sub_bytes, pl.subsequences, pl.sequences, 0, 0,
+                                         pl.path == PSN_JPEG_PATH_PARALLEL ? 0 : P.a.nblocks},
+                          P.a.nblocks, it.stats, it.coef};
+        if (pl.path == PSN_JPEG_PATH_PARALLEL) sub = pl.sub_bytes;
+    }
+    for (int k = 0; k < L.n_parallel; k++) hl[k] = L.parallel[k];
+    for (int k = 0; k < L.n_serial; k++) hl[n + k] = L.serial[k];
+    JCHK(c, hipMemcpyAsync(c->d_blob, c->h_blob, L.blob_size, hipMemcpyHostToDevice, c->stream));
+    JCHK(c, hipEventRecord(c->blob_free, c->stream));
+    c->blob_pending = true;
+    JCHK(c, hipMemsetAsync(c->d_coef, 0, L.coef_size, c->stream));
+    c->batch = rec;
+    c->last = rec.back().st;
+    c->decoded = true;
+    c->last_nblocks = rec.back().nblocks;
+    c->last_stats_off = rec.back().stats_off;
+    c->last_coef_off = rec.back().coef_off;
+    const psn::EntArgs *de = (const psn::EntArgs *)(c->d_blob + L.ent_args);
+    const psn::JpegArgs *da = (const psn::JpegArgs *)(c->d_blob + L.jpeg_args);
+    const int *dl = (const int *)(c->d_blob + L.lists);
+    if (L.n_parallel) {
+        const size_t staged = sub <= PSN_JPEG_STAGE_MAX_SUB ? (size_t)jent::kSeqLen * sub + psn::kStageSlack : 0;
+        const size_t lds_sync = sizeof(psn::LdsTabs) + jent::kSeqLen * 8 + staged, lds_emit = sizeof(psn::LdsTabs) + psn::kNaturalLds + staged;
+        const dim3 seqs(L.max_sequences, L.n_parallel);
+        hipLaunchKernelGGL(psn::jpeg_sync_batch_kernel, seqs, dim3(jent::kSeqLen), lds_sync, c->stream, de, dl);
+        JCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(psn::jpeg_chain_batch_kernel, dim3(1, L.n_parallel), dim3(1024), 0, c->stream, de, dl);
+        JCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(psn::jpeg_emit_batch_kernel, seqs, dim3(jent::kSeqLen), lds_emit, c->stream, de, dl);
+        JCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(psn::jpeg_dc_batch_kernel, dim3(L.max_parallel_components, L.n_parallel), dim3(1024), 0, c->stream, de, dl);
+        JCHK(c, hipGetLastError());
+    }
+    if (L.n_serial) {
+        hipLaunchKernelGGL(psn::jpeg_entropy_batch_kernel, dim3(L.max_segment_groups, L.n_serial), dim3(64), 0, c->stream, da, dl + n);
+        JCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(psn::jpeg_idct_batch_kernel, dim3(L.max_block_groups, n), dim3(256), 0, c->stream, da);
+    JCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(psn::jpeg_color_batch_kernel, dim3((L.max_width + 255) / 256, L.max_height, n), dim3(256), 0, c->stream, da);
+    JCHK(c, hipGetLastError());
+    return PSN_LK_OK;
+}
+
+int psn_jpeg_batch_stats(psn_jpeg_ctx *c, int item, psn_jpeg_stats *out) {
+    if (!c || !out) return PSN_LK_ERR_ARG;
+    if (item < 0 || (size_t)item >= c->batch.size())
+        return jerr(c, PSN_LK_ERR_ARG, "item %d: the last decode was %s", item, c->batch.empty() ? "not a batch" : "a smaller batch");
+    JCHK(c, hipSetDevice(c->device));
+    JCHK(c, hipStreamSynchronize(c->stream));
+    const psn_jpeg_ctx::BatchItem &b = c->batch[(size_t)item];
+    *out = b.st;
+    if (b.st.path == PSN_JPEG_PATH_PARALLEL) {
+        psn::DevStats d;
+        JCHK(c, hipMemcpy(&d, c->d_par + b.stats_off, sizeof d, hipMemcpyDeviceToHost));
+        out->sync_rounds = d.sync_rounds;
+        out->chain_rounds = d.chain_rounds;
+        out->blocks = d.blocks;
+    }
+    return PSN_LK_OK;
+}
+
+int psn_jpeg_debug_read_batch_coefficients(psn_jpeg_ctx *c, int item, int16_t *out, size_t count) {
+    if (!c || !out) return PSN_LK_ERR_ARG;
+    if (item < 0 || (size_t)item >= c->batch.size())
+        return jerr(c, PSN_LK_ERR_ARG, "item %d: the last decode was %s", item, c->batch.empty() ? "not a batch" : "a smaller batch");
+    const psn_jpeg_ctx::BatchItem &b = c->batch[(size_t)item];
+    if (count != (size_t)b.nblocks * 64) return jerr(c, PSN_LK_ERR_ARG, "count %zu is not %d blocks * 64", count, b.nblocks);
+    JCHK(c, hipSetDevice(c->device));
+    JCHK(c, hipMemcpyAsync(out, (const uint8_t *)c->d_coef + b.coef_off, count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    JCHK(c, hipStreamSynchronize(c->stream));
+    return PSN_LK_OK;
+}
+
 int psn_jpeg_debug_set_entropy(psn_jpeg_ctx *c, int mode, int sub_bytes) {
     if (!c) return PSN_LK_ERR_ARG;
     if (!psn::valid_entropy_request(mode, sub_bytes))
@@ -759,7 +920,7 @@ int psn_jpeg_debug_read_coefficients(psn_jpeg_ctx *c, int16_t *out, size_t count
     if (count != (size_t)c->last_nblocks * 64)
         return jerr(c, PSN_LK_ERR_ARG, "count %zu is not %d blocks * 64", count, c->last_nblocks);
     JCHK(c, hipSetDevice(c->device));
-    JCHK(c, hipMemcpyAsync(out, c->d_coef, count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    JCHK(c, hipMemcpyAsync(out, (const uint8_t *)c->d_coef + c->last_coef_off, count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
     JCHK(c, hipStreamSynchronize(c->stream));
     return PSN_LK_OK;
 }
@@ -772,7 +933,7 @@ int psn_jpeg_last_stats(psn_jpeg_ctx *c, psn_jpeg_stats *out) {
     *out = c->last;
     if (c->last.path == PSN_JPEG_PATH_PARALLEL) {
         psn::DevStats d;
-        JCHK(c, hipMemcpy(&d, c->d_par, sizeof d, hipMemcpyDeviceToHost));
+        JCHK(c, hipMemcpy(&d, c->d_par + c->last_stats_off, sizeof d, hipMemcpyDeviceToHost));
         out->sync_rounds = d.sync_rounds;
         out->chain_rounds = d.chain_rounds;
         out->blocks = d.blocks;

@@ -211,9 +211,148 @@ void entropy_geometry(const Parsed &P, jent::Geo &G, int &nb0, int &bpm) {
     G.total = a.nmcu * bpm;
 }
 
+static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+int plan_batch(const psn_jpeg_item *items, int n, int mode, int sub, Batch &B, std::string &why) {
+    psn_jpeg_batch_layout &L = B.L;
+    memset(&L, 0, sizeof L);
+    L.bad_item = -1;
+    if (!items) return why = "null item list", PSN_LK_ERR_ARG;
+    if (n < 1 || n > PSN_JPEG_MAX_BATCH)
+        return why = "batch of " + std::to_string(n) + " items (1.." + std::to_string(PSN_JPEG_MAX_BATCH) + ")", PSN_LK_ERR_ARG;
+    B.P.assign((size_t)n, Parsed());
+    B.plans.assign((size_t)n, psn_jpeg_plan());
+    for (int i = 0; i < n; i++) {  // every item is checked before anything is laid out
+        const std::string at = "item " + std::to_string(i) + ": ";
+        L.bad_item = i;
+        if (!items[i].data || !items[i].d_bgr) return why = at + "null pointer", PSN_LK_ERR_ARG;
+        std::string w;
+        const int rc = parse(items[i].data, items[i].len, B.P[(size_t)i], w);
+        if (rc) return why = at + w, rc;
+        if (items[i].stride < 3 * B.P[(size_t)i].a.W)
+            return why = at + "stride " + std::to_string(items[i].stride) + " < 3 * width " + std::to_string(B.P[(size_t)i].a.W),
+                   PSN_LK_ERR_ARG;
+        plan_entropy(B.P[(size_t)i], mode, sub, B.plans[(size_t)i]);
+    }
+    L.n = n;
+    size_t blob = 0, par = 0, coef = 0, planes = 0;
+    for (int i = 0; i < n; i++) {
+        const Parsed &P = B.P[(size_t)i];
+        const psn_jpeg_plan &pl = B.plans[(size_t)i];
+        psn_jpeg_batch_item_layout &it = L.item[i];
+        it.path = pl.path;
+        it.tables = blob;
+        blob += up16(sizeof(Tables));
+        it.segments = blob;
+        it.segments_size = up16(4 * P.seg.size());
+        blob += it.segments_size;
+        it.bytes = blob;
+        it.bytes_size = up16((size_t)P.a.data_len) + 16;  // the item's own zeroed slack
+        blob += it.bytes_size;
+        it.stats = par;
+        par += up16(sizeof(DevStats));
+        if (pl.path == PSN_JPEG_PATH_PARALLEL) {
+            const size_t nsub = (size_t)pl.subsequences, nseq = (size_t)pl.sequences;
+            it.list_index = L.n_parallel;
+            L.parallel[L.n_parallel++] = i;
+            it.states_size = up16(8 * nsub);
+            it.counts_size = it.prefix_size = up16(4 * nsub);
+            it.rounds_size = up16(4 * nseq);
+            L.max_sequences = std::max(L.max_sequences, pl.sequences);
+            L.max_parallel_components = std::max(L.max_parallel_components, P.a.nc);
+        } else {
+            it.list_index = L.n_serial;
+            L.serial[L.n_serial++] = i;
+            L.max_segment_groups = std::max(L.max_segment_groups, (P.a.nseg + 63) / 64);
+        }
+        it.states = par;
+        par += it.states_size;
+        it.counts = par;
+        par += it.counts_size;
+        it.prefix = par;
+        par += it.prefix_size;
+        it.rounds = par;
+        par += it.rounds_size;
+        it.coef = coef;
+        it.coef_size = (size_t)P.a.nblocks * 64 * sizeof(int16_t);  // a multiple of 128
+        coef += it.coef_size;
+        it.planes = planes;
+        it.planes_size = (size_t)P.a.nblocks * 64;
+        planes += it.planes_size;
+        L.max_block_groups = std::max(L.max_block_groups, (P.a.nblocks + 255) / 256);
+        L.max_width = std::max(L.max_width, P.a.W);
+        L.max_height = std::max(L.max_height, P.a.H);
+    }
+    L.ent_args = blob;
+    blob += up16((size_t)n * sizeof(EntArgs));
+    L.jpeg_args = blob;
+    blob += up16((size_t)n * sizeof(JpegArgs));
+    L.lists = blob;
+    blob += up16(2 * (size_t)n * sizeof(int));  // [parallel | serial]
+    L.blob_size = blob;
+    L.scratch_size = par;
+    L.coef_size = coef;
+    L.planes_size = planes;
+    // one memset and one copy take the totals; the tools that read the buffers index them with int
+    if (coef > (size_t)INT_MAX || blob > (size_t)INT_MAX) {
+        L.bad_item = -1;
+        return why = "frame too large (batch of " + std::to_string(n) + ")", PSN_LK_ERR_UNSUPPORTED;
+    }
+    L.bad_item = -1;
+    return PSN_LK_OK;
+}
+
+void batch_args(const Batch &B, int i, const psn_jpeg_item &item, uint8_t *blob, uint8_t *par, uint8_t *coef,
+                uint8_t *planes, JpegArgs &a, EntArgs &e) {
+    const Parsed &P = B.P[(size_t)i];
+    const psn_jpeg_plan &pl = B.plans[(size_t)i];
+    const psn_jpeg_batch_item_layout &it = B.L.item[i];
+    a = P.a;
+    a.tab = (const Tables *)(blob + it.tables);
+    a.seg = (const int *)(blob + it.segments);
+    a.data = blob + it.bytes;
+    a.coef = (int16_t *)(coef + it.coef);
+    a.planes = planes + it.planes;
+    a.out = item.d_bgr;
+    a.out_stride = item.stride;
+    memset(&e, 0, sizeof e);
+    if (pl.path != PSN_JPEG_PATH_PARALLEL) return;
+    e.tab = a.tab;
+    e.data = a.data;
+    e.len = a.data_len;
+    e.S = pl.sub_bytes;
+    e.nsub = pl.subsequences;
+    e.nseq = pl.sequences;
+    e.stage = pl.sub_bytes <= PSN_JPEG_STAGE_MAX_SUB ? 1 : 0;
+    entropy_geometry(P, e.geo, e.nb0, e.bpm);
+    e.nmcu = a.nmcu;
+    for (int c = 0; c < a.nc; c++) {
+        e.td[c] = a.c[c].td;
+        e.ta[c] = a.c[c].ta;
+    }
+    e.stats = (DevStats *)(par + it.stats);
+    e.st = (unsigned long long *)(par + it.states);
+    e.cnt = (unsigned *)(par + it.counts);
+    e.pre = (unsigned *)(par + it.prefix);
+    e.seq_rounds = (int *)(par + it.rounds);
+    e.coef = a.coef;
+}
+
 }  // namespace psn
 
 extern "C" {
+
+int psn_jpeg_batch_plan(const psn_jpeg_item *items, int n, psn_jpeg_batch_layout *out, psn_jpeg_plan *plans) {
+    if (!out) return PSN_LK_ERR_ARG;
+    psn::Batch B;
+    std::string why;
+    const int rc = psn::plan_batch(items, n, 0, 0, B, why);
+    *out = B.L;
+    if (rc) return rc;
+    if (plans)
+        for (int i = 0; i < n; i++) plans[i] = B.plans[(size_t)i];
+    return PSN_LK_OK;
+}
 
 int psn_jpeg_info(const uint8_t *data, size_t len, int *w, int *h, int *comps) {
     if (!data || !w || !h) return PSN_LK_ERR_ARG;

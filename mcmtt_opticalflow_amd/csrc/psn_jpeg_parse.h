@@ -46,6 +46,36 @@ struct JpegArgs {
     int nblocks;
 };
 
+// ---- parallel path: what its kernels take (psn_jpeg.hip) -------------------
+struct DevStats {           // written by the kernels, read by psn_jpeg_last_stats / psn_jpeg_batch_stats
+    int sync_rounds, chain_rounds, blocks, pad;
+};
+
+struct EntArgs {
+    const Tables *tab;
+    const uint8_t *data;     // entropy bytes (readable 16 bytes past len)
+    long long len;
+    int S;                   // subsequence bytes
+    int nsub, nseq;          // subsequences, sequences of jent::kSeqLen
+    int stage;               // 1: the workgroup's bytes are staged in LDS
+    int nb0, bpm, nmcu;
+    int td[kJpegMaxComp], ta[kJpegMaxComp];
+    jent::Geo geo;
+    unsigned long long *st;  // [nsub] exit state
+    unsigned *cnt;           // [nsub] blocks completed inside the subsequence
+    unsigned *pre;           // [nsub] exclusive prefix sum of cnt
+    int *seq_rounds;         // [nseq] rounds of jpeg_sync_kernel's workgroup
+    DevStats *stats;
+    int16_t *coef;
+};
+
+// Bytes of a workgroup's subsequences are staged in LDS up to this subsequence
+// size (256 subsequences + tables + states stay under 64 KiB); larger ones are
+// read from global memory.
+#ifndef PSN_JPEG_STAGE_MAX_SUB
+#define PSN_JPEG_STAGE_MAX_SUB 128
+#endif
+
 // A parsed frame: tables, geometry, entropy segments.
 struct Parsed {
     Tables tab;
@@ -84,6 +114,24 @@ void plan_entropy(const Parsed &P, int mode, int sub, psn_jpeg_plan &pl);
 
 // The scan's block layout as the symbol step's sinks address it.
 void entropy_geometry(const Parsed &P, jent::Geo &G, int &nb0, int &bpm);
+
+// A batch (psn_jpeg_decode_batch_device): the parsed items, their plans and where
+// each item's tables, bytes, scratch, coefficients and planes lie.
+struct Batch {
+    std::vector<Parsed> P;
+    std::vector<psn_jpeg_plan> plans;
+    psn_jpeg_batch_layout L;
+};
+
+// Checks and parses every item, plans it (mode, sub: psn_jpeg_debug_set_entropy)
+// and lays the batch out. On an error B.L.bad_item is the first bad item (-1: the
+// call's own arguments) and `why` names it.
+int plan_batch(const psn_jpeg_item *items, int n, int mode, int sub, Batch &B, std::string &why);
+
+// The kernels' arguments of item i of a planned batch, over the base addresses of
+// the device blob, the parallel scratch, the coefficients and the planes.
+void batch_args(const Batch &B, int i, const psn_jpeg_item &it, uint8_t *blob, uint8_t *par, uint8_t *coef,
+                uint8_t *planes, JpegArgs &a, EntArgs &e);
 
 #pragma GCC visibility pop
 

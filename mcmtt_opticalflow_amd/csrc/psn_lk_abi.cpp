@@ -667,10 +667,61 @@ int psn_lk_push_frame_jpeg(psn_lk_ctx *c, int slot, const uint8_t *jpeg, size_t 
     return ingest_build(c, slot, c->d_stage[slot], (int)row, 3, c->ingest_stream);
 }
 
+int psn_lk_push_frames_jpeg(psn_lk_ctx *c, const int *slots, const uint8_t *const *jpeg, const size_t *len, int n) {
+    if (!c || !slots || !jpeg || !len) return PSN_LK_ERR_ARG;
+    if (n < 1 || n > PSN_JPEG_MAX_BATCH) return set_err(c, PSN_LK_ERR_ARG, "%d frames (1..%d)", n, PSN_JPEG_MAX_BATCH);
+    for (int i = 0; i < n; i++) {  // every frame is checked before any slot is touched
+        if (!jpeg[i]) return set_err(c, PSN_LK_ERR_ARG, "item %d: null frame", i);
+        if (check_user_slot(c, slots[i])) return set_err(c, PSN_LK_ERR_SLOT, "item %d: slot %d out of range", i, slots[i]);
+        for (int k = 0; k < i; k++)
+            if (slots[k] == slots[i]) return set_err(c, PSN_LK_ERR_SLOT, "item %d: slot %d repeats item %d's", i, slots[i], k);
+        int w = 0, h = 0;
+        const int rc = psn_jpeg_info(jpeg[i], len[i], &w, &h, nullptr);
+        if (rc) return set_err(c, rc, "item %d: JPEG headers", i);
+        if (w != c->src_w || h != c->src_h)
+            return set_err(c, PSN_LK_ERR_ARG, "item %d: JPEG %dx%d, context %dx%d", i, w, h, c->src_w, c->src_h);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = flush_pending(c);
+    if (rc) return rc;
+    if (!c->jpeg) {
+        if ((rc = psn_jpeg_create(c->device, &c->jpeg))) return set_err(c, rc, "psn_jpeg_create");
+        psn_jpeg_set_stream(c->jpeg, c->ingest_stream);
+    }
+    const size_t row = (size_t)c->src_w * 3;
+    for (int i = 0; i < n; i++)
+        if ((rc = ensure_stage(c, slots[i], row * c->src_h))) return rc;
+    psn_jpeg_item items[PSN_JPEG_MAX_BATCH];
+    for (int i = 0; i < n; i++) {
+        // as psn_lk_push_frame_jpeg: the decode overwrites a staging buffer only after
+        // the slot's readers and its previous build
+        if ((rc = c->slots.wait_free(slots[i], c->ingest_stream))) return rc;
+        if ((rc = c->slots.wait_prev_build(slots[i], c->ingest_stream))) return rc;
+        items[i] = {jpeg[i], len[i], c->d_stage[slots[i]], (int)row};
+    }
+    rc = psn_jpeg_decode_batch_device(c->jpeg, items, n);
+    if (rc) return set_err(c, rc, "JPEG decode: %s", psn_jpeg_last_error(c->jpeg));
+    for (int i = 0; i < n; i++) {
+        const int slot = slots[i];
+        c->filled[slot] = 1;
+        c->color_src[slot] = {c->d_stage[slot], (int)row, 3, false, 0};
+        if ((rc = ingest_build(c, slot, c->d_stage[slot], (int)row, 3, c->ingest_stream))) return rc;
+    }
+    return PSN_LK_OK;
+}
+
 int psn_lk_jpeg_last_stats(psn_lk_ctx *c, struct psn_jpeg_stats *out) {
     if (!c || !out) return PSN_LK_ERR_ARG;
     if (!c->jpeg) return set_err(c, PSN_LK_ERR_ARG, "no JPEG frame pushed yet");
     const int rc = psn_jpeg_last_stats(c->jpeg, out);
+    if (rc) return set_err(c, rc, "JPEG stats: %s", psn_jpeg_last_error(c->jpeg));
+    return PSN_LK_OK;
+}
+
+int psn_lk_jpeg_batch_stats(psn_lk_ctx *c, int item, struct psn_jpeg_stats *out) {
+    if (!c || !out) return PSN_LK_ERR_ARG;
+    if (!c->jpeg) return set_err(c, PSN_LK_ERR_ARG, "no JPEG frame pushed yet");
+    const int rc = psn_jpeg_batch_stats(c->jpeg, item, out);
     if (rc) return set_err(c, rc, "JPEG stats: %s", psn_jpeg_last_error(c->jpeg));
     return PSN_LK_OK;
 }

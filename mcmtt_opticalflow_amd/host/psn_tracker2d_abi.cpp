@@ -514,6 +514,11 @@ int psn_t2d_group_push_frame_device(psn_t2d_group *g, int cam, const uint8_t *de
     return gset(g, g->flow.StageFrame((size_t)cam, dev_frame, stride, channels, true));
 }
 
+int psn_t2d_group_push_frames_jpeg(psn_t2d_group *g, const uint8_t *const *jpeg, const size_t *len) {
+    if (!g || !jpeg || !len) return PSN_LK_ERR_ARG;
+    return gset(g, g->flow.StageFramesJpeg(jpeg, len));
+}
+
 int psn_t2d_group_push_frame_jpeg(psn_t2d_group *g, int cam, const uint8_t *jpeg, size_t len) {
     if (!g || cam < 0 || (size_t)cam >= g->io().size() || !jpeg) return PSN_LK_ERR_ARG;
     return gset(g, g->flow.StageFrameJpeg((size_t)cam, jpeg, len));

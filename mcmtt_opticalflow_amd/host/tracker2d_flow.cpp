@@ -152,6 +152,22 @@ int Tracker2DFlow::StageFrameJpeg(size_t cam, const uint8_t *jpeg, size_t len) {
     return PSN_LK_OK;
 }
 
+int Tracker2DFlow::StageFramesJpeg(const uint8_t *const *jpeg, const size_t *len) {
+    if (!lk_ || !jpeg || !len) return PSN_LK_ERR_ARG;
+    std::vector<int> slots(cams_.size());
+    for (size_t cam = 0; cam < cams_.size(); cam++) {
+        const int rc = NextStagingSlot(cam, &slots[cam]);
+        if (rc) return rc;
+    }
+    const int rc = psn_lk_push_frames_jpeg(lk_, slots.data(), jpeg, len, (int)slots.size());
+    if (rc) return fail(rc, "stage JPEG frames");
+    for (size_t cam = 0; cam < cams_.size(); cam++) {  // committed only now: the whole push succeeded
+        filled_[(size_t)slots[cam]] = 1;
+        cams_[cam].nstaged++;
+    }
+    return PSN_LK_OK;
+}
+
 int Tracker2DFlow::DetectFeatures(const std::vector<Detection> &dets, uint32_t seed,
                                   std::vector<std::vector<Point2f>> &features) {
     if (!lk_) return PSN_LK_ERR_ARG;

@@ -80,6 +80,7 @@ class Tracker2DFlow {
     // is staged (a pipelined driver uploads two frames ahead).
     int StageFrame(size_t cam, const uint8_t *frame, int stride, int channels, bool on_device);
     int StageFrameJpeg(size_t cam, const uint8_t *jpeg, size_t len);  // a baseline JPEG, decoded on the device
+    int StageFramesJpeg(const uint8_t *const *jpeg, const size_t *len);  // one per camera, one batched decode; all or nothing
     int NextStagingSlot(size_t cam, int *slot);
     struct CamFrame {  // one camera's inputs and outputs of Run
         std::vector<Detection> dets;                      // height-validated detections of frame t

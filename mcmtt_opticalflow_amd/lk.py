@@ -178,6 +178,23 @@ class LKContext:
         buf = ctypes.create_string_buffer(bytes(data), len(data))
         self._check(self._L.psn_lk_push_frame_jpeg(self._h, slot, buf, len(data)), "push_frame_jpeg")
 
+    def push_frames_jpeg(self, slots, files):
+        """One JPEG per slot, decoded in one batched device pass (psn_lk_push_frames_jpeg);
+        all or nothing."""
+        n = len(files)
+        assert len(slots) == n
+        bufs = [ctypes.create_string_buffer(bytes(f), len(f)) for f in files]
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[ctypes.addressof(b) for b in bufs])
+        lens = (ctypes.c_size_t * max(n, 1))(*[len(f) for f in files])
+        self._check(self._L.psn_lk_push_frames_jpeg(self._h, (ctypes.c_int * max(n, 1))(*slots), ptrs, lens, n),
+                    "push_frames_jpeg")
+
+    def jpeg_batch_stats(self, item: int) -> dict:
+        """psn_lk_jpeg_batch_stats: jpeg_stats of frame `item` of the last push_frames_jpeg."""
+        s = _lib.JpegStats()
+        self._check(self._L.psn_lk_jpeg_batch_stats(self._h, item, ctypes.byref(s)), "jpeg_batch_stats")
+        return _lib.struct_dict(s)
+
     def jpeg_stats(self) -> dict:
         """psn_lk_jpeg_last_stats: the entropy path of the last push_frame_jpeg and its round counters."""
         s = _lib.JpegStats()
@@ -487,6 +504,78 @@ class JpegDecoder:
         if rc != 0:
             raise PsnLkError(rc, "psn_jpeg_info")
         return w.value, h.value, c.value
+
+    @staticmethod
+    def _items(files, ptrs=None, strides=None):
+        """(psn_jpeg_item array, the buffers it points into)."""
+        n = len(files)
+        keep = [None if f is None else ctypes.create_string_buffer(bytes(f), len(f)) for f in files]
+        items = (_lib.JpegItem * max(n, 1))()
+        for i, f in enumerate(files):
+            if f is None:  # a null data pointer (the refusal's test)
+                items[i] = _lib.JpegItem(None, 0, ptrs[i] if ptrs else 16, strides[i] if strides else 0)
+                continue
+            items[i] = _lib.JpegItem(ctypes.addressof(keep[i]), len(f), ptrs[i] if ptrs else 16,
+                                     strides[i] if strides else 1 << 30)
+        return items, keep
+
+    @staticmethod
+    def batch_plan(files, strides=None, n=None) -> dict:
+        """psn_jpeg_batch_plan (host only): {"rc", "layout" (psn_jpeg_batch_layout as a dict,
+        "item" trimmed to the batch), "plans"}. A None file is a null pointer; strides
+        default to wide enough; n overrides the item count handed to the library."""
+        items, keep = JpegDecoder._items(files, strides=strides)
+        n = len(files) if n is None else n
+        lay = _lib.JpegBatchLayout()
+        plans = (_lib.JpegPlan * max(len(files), 1))()
+        rc = _lib.load().psn_jpeg_batch_plan(items, n, ctypes.byref(lay), plans)
+        d = _lib.struct_dict(lay)
+        d["parallel"], d["serial"] = list(lay.parallel)[:lay.n_parallel], list(lay.serial)[:lay.n_serial]
+        d["item"] = [_lib.struct_dict(lay.item[i]) for i in range(lay.n)]
+        return {"rc": rc, "layout": d, "plans": [_lib.struct_dict(plans[i]) for i in range(lay.n)] if rc == 0 else []}
+
+    def decode_batch(self, files) -> list:
+        """psn_jpeg_decode_batch_device into a device buffer of the call's own:
+        one (H, W, 3) u8 BGR array per file."""
+        from . import hip
+
+        sizes, offs, total = [], [], 0
+        for f in files:
+            try:
+                w, h, _ = self.info(bytes(f))
+            except PsnLkError:
+                w, h = 8, 8  # the batch call names the bad item itself
+            sizes.append((w, h))
+            offs.append(total)
+            total += (3 * w * h + 255) & ~255
+        buf = hip.DeviceBuffer(total)
+        try:
+            items, keep = self._items(files, [buf.addr + o for o in offs], [3 * w for w, _ in sizes])
+            rc = self._L.psn_jpeg_decode_batch_device(self._h, items, len(files))
+            if rc != 0:
+                raise PsnLkError(rc, f"psn_jpeg_decode_batch_device: {self._L.psn_jpeg_last_error(self._h).decode()}")
+            self.batch_stats(len(files) - 1)  # waits for the decoder's stream
+            flat = buf.to_array((total,), np.uint8)
+        finally:
+            buf.free()
+        return [flat[o:o + 3 * w * h].reshape(h, w, 3).copy() for o, (w, h) in zip(offs, sizes)]
+
+    def batch_stats(self, item: int) -> dict:
+        """psn_jpeg_batch_stats: stats() of item `item` of the last batch."""
+        s = _lib.JpegStats()
+        rc = self._L.psn_jpeg_batch_stats(self._h, item, ctypes.byref(s))
+        if rc != 0:
+            raise PsnLkError(rc, f"psn_jpeg_batch_stats: {self._L.psn_jpeg_last_error(self._h).decode()}")
+        return _lib.struct_dict(s)
+
+    def batch_coefficients(self, item: int) -> np.ndarray:
+        """psn_jpeg_debug_read_batch_coefficients: coefficients() of item `item` of the last batch."""
+        coef = np.empty((self.batch_stats(item)["blocks"], 64), np.int16)
+        rc = self._L.psn_jpeg_debug_read_batch_coefficients(self._h, item, coef.ctypes.data, coef.size)
+        if rc != 0:
+            raise PsnLkError(rc, "psn_jpeg_debug_read_batch_coefficients: "
+                             f"{self._L.psn_jpeg_last_error(self._h).decode()}")
+        return coef
 
     def decode(self, data: bytes) -> np.ndarray:
         """(H, W, 3) u8 BGR, as cv::imread(..., IMREAD_COLOR) returns it."""

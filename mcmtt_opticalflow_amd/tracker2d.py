@@ -194,6 +194,8 @@ def load():
     L.psn_t2d_group_push_frame.argtypes = [vp, ip, vp, ip, ip]
     L.psn_t2d_group_push_frame_device.argtypes = [vp, ip, vp, ip, ip]
     L.psn_t2d_group_push_frame_jpeg.argtypes = [vp, ip, vp, ctypes.c_size_t]
+    if hasattr(L, "psn_t2d_group_push_frames_jpeg"):  # (absent from the A/B experiments' older builds only)
+        L.psn_t2d_group_push_frames_jpeg.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
     L.psn_t2d_group_launch.argtypes = [vp, ctypes.c_uint, vp, vp, ip, ctypes.c_uint32]
     L.psn_t2d_group_complete.argtypes = [vp, vp, vp, ctypes.POINTER(Track2DResult)]
     L.psn_t2d_group_run.argtypes = [vp, ctypes.c_uint, vp, vp, ip, ctypes.c_uint32, ctypes.POINTER(Track2DResult)]
@@ -522,6 +524,15 @@ class Group:
         self._check(self._L.psn_t2d_group_push_frame_jpeg(self._h, cam, data if isinstance(data, bytes) else
                                                           ctypes.c_void_p(data.ctypes.data), len(data)),
                     "push_frame_jpeg")
+
+    def push_frames_jpeg(self, files):
+        """Every camera's frame t as a baseline JPEG file (bytes), one per camera in camera
+        order, decoded in one batched device pass (psn_t2d_group_push_frames_jpeg)."""
+        assert len(files) == self.ncams
+        bufs = [ctypes.create_string_buffer(bytes(f), len(f)) for f in files]
+        ptrs = (ctypes.c_void_p * self.ncams)(*[ctypes.addressof(b) for b in bufs])
+        lens = (ctypes.c_size_t * self.ncams)(*[len(f) for f in files])
+        self._check(self._L.psn_t2d_group_push_frames_jpeg(self._h, ptrs, lens), "push_frames_jpeg")
 
     def push_frame_device(self, cam: int, dev_ptr: int, stride: int, channels: int = 1):
         self._check(self._L.psn_t2d_group_push_frame_device(self._h, cam, ctypes.c_void_p(dev_ptr), stride, channels),
