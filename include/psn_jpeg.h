@@ -53,7 +53,9 @@ int psn_jpeg_set_stream(psn_jpeg_ctx *ctx, void *hip_stream);
 
 /* Decode into device memory: d_bgr receives height rows of width*3 bytes,
  * `stride` bytes apart. Asynchronous on the decoder's stream; `data` is copied
- * before the call returns. */
+ * before the call returns. A batch of one (psn_jpeg_decode_batch_device below:
+ * the same staging blob, the same kernel entries), but for its error texts,
+ * which name no item, and psn_jpeg_batch_stats, for which it is no batch. */
 int psn_jpeg_decode_device(psn_jpeg_ctx *ctx, const uint8_t *data, size_t len, uint8_t *d_bgr, int stride);
 /* The same into host memory (synchronous). */
 int psn_jpeg_decode(psn_jpeg_ctx *ctx, const uint8_t *data, size_t len, uint8_t *bgr, int stride);
@@ -115,10 +117,11 @@ int psn_jpeg_debug_read_coefficients(psn_jpeg_ctx *ctx, int16_t *out, size_t cou
 
 /* The frames of one frame-set (one file per camera) decoded in one device pass:
  * one pinned staging blob and one H2D copy for all items, one memset, and one
- * fixed number of kernel launches whatever n -- every kernel has a batch entry
+ * fixed number of kernel launches whatever n -- every kernel has one entry,
  * whose grid carries the item index and whose workgroups past an item's own
  * extent return at once. Items may differ in size, components, subsampling and
- * entropy path; every item's output is that of psn_jpeg_decode_device alone. */
+ * entropy path; every item's output is that of psn_jpeg_decode_device alone,
+ * which is this decode at n = 1. */
 #define PSN_JPEG_MAX_BATCH 64
 typedef struct psn_jpeg_item {
     const uint8_t *data;

@@ -4,7 +4,7 @@
 //   host   markers -> quantisation tables (natural order), Huffman tables
 //          (canonical maxcode/valoffset + a 9-bit lookahead table), component
 //          geometry, restart-segment byte offsets (RSTn positions); one pinned
-//          staging block [tables | segment offsets | entropy bytes] -> one H2D
+//          staging block (its layout: "items" below) -> one H2D
 //   K1     jpeg_entropy_kernel: one thread per restart segment decodes its MCUs
 //          (jdhuff.c: fill with 0xFF00 unstuffing, a marker feeds zeros; DC
 //          prediction reset per segment) into int16 coefficient blocks
@@ -30,8 +30,10 @@
 //   K3     jpeg_color_kernel: one thread per pixel: fancy upsampling (jdsample.c
 //          h2v1 / h2v2, edges replicated at the downsampled size), YCbCr->RGB
 //          (jdcolor.c, SCALEBITS 16), BGR out
-//   batch  psn_jpeg_decode_batch_device: every kernel has a *_batch_kernel entry
-//          over the same body, the item index in the grid; one blob
+//   items  every decode is a batch (psn_jpeg_decode_batch_device; a single image,
+//          psn_jpeg_decode_device, is a batch of one): each kernel has one entry,
+//          which reads its item's arguments from a device table, the item index
+//          in the grid; one blob
 //          [per item: tables | segment offsets | entropy bytes + 16 zeroed bytes]
 //          [EntArgs table | JpegArgs table | parallel list | serial list], one
 //          H2D, one memset, one launch per kernel whatever the item count
@@ -127,10 +129,9 @@ struct BitReader {
 
 __device__ __forceinline__ int extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
 
-// Every kernel's body is a device function over its argument struct and the
-// indices a single-image launch reads from blockIdx: the single-image entry
-// passes its by-value argument and blockIdx, the batch entry (the end of the
-// namespace) an item's arguments from a device table and the item's own index.
+// Every kernel's body is a device function over one item's argument struct and
+// the item's own indices; the entry (the end of the namespace) passes it the
+// item's arguments from a device table.
 __device__ __forceinline__ void entropy_body(const JpegArgs &A, int group) {
     const int s = group * blockDim.x + threadIdx.x;
     if (s >= A.nseg) return;
@@ -171,8 +172,6 @@ __device__ __forceinline__ void entropy_body(const JpegArgs &A, int group) {
         }
     }
 }
-
-__global__ __launch_bounds__(64) void jpeg_entropy_kernel(JpegArgs A) { entropy_body(A, blockIdx.x); }
 
 // ---------------------------------------------------------------- parallel path
 // Subsequence i owns the bits [i * 8S, (i + 1) * 8S) of the entropy bytes: its
@@ -272,11 +271,6 @@ __device__ __forceinline__ void sync_body(const EntArgs &E, int seq, uint8_t *sm
     if (t == 0) E.seq_rounds[seq] = rounds;
 }
 
-__global__ __launch_bounds__(256) void jpeg_sync_kernel(EntArgs E) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    sync_body(E, blockIdx.x, smem);
-}
-
 // Inclusive scan over the workgroup (any multiple of 64 threads up to 1024);
 // `ws` holds one word per wave. Every thread calls it.
 __device__ __forceinline__ unsigned block_scan_incl(unsigned v, unsigned *ws, unsigned *total) {
@@ -368,8 +362,6 @@ __device__ __forceinline__ void chain_body(const EntArgs &E) {
     }
 }
 
-__global__ __launch_bounds__(1024) void jpeg_chain_kernel(EntArgs E) { chain_body(E); }
-
 __device__ __forceinline__ void emit_body(const EntArgs &E, int seq, uint8_t *smem) {
     LdsTabs &L = *(LdsTabs *)smem;
     uint8_t *snat = smem + sizeof(LdsTabs);  // the natural-order table: a divergent lookup per coefficient
@@ -392,11 +384,6 @@ __device__ __forceinline__ void emit_body(const EntArgs &E, int seq, uint8_t *sm
     if (last) E.stats->blocks = (int)min(sink.g, total);
 }
 
-__global__ __launch_bounds__(256) void jpeg_emit_kernel(EntArgs E) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    emit_body(E, blockIdx.x, smem);
-}
-
 __device__ __forceinline__ void dc_body(const EntArgs &E, int ci) {
     __shared__ unsigned ws[16];
     const long long n = (long long)E.nmcu * E.geo.c[ci].h * E.geo.c[ci].v;
@@ -412,8 +399,6 @@ __device__ __forceinline__ void dc_body(const EntArgs &E, int ci) {
         last_dc += tot;
     }
 }
-
-__global__ __launch_bounds__(1024) void jpeg_dc_kernel(EntArgs E) { dc_body(E, blockIdx.x); }
 
 __device__ __forceinline__ long long desc(long long x, int n) { return (x + (1LL << (n - 1))) >> n; }
 __device__ __forceinline__ uint8_t range_limit(long long v) {
@@ -485,8 +470,6 @@ __device__ __forceinline__ void idct_body(const JpegArgs &A, int group) {
     }
 }
 
-__global__ __launch_bounds__(256) void jpeg_idct_kernel(JpegArgs A) { idct_body(A, blockIdx.x); }
-
 // One fancy-upsampled chroma sample at full-resolution (x, y).
 __device__ __forceinline__ int chroma(const JpegArgs &A, const CompGeo &g, int x, int y) {
     const uint8_t *pl = A.planes + g.plane0;
@@ -531,54 +514,52 @@ __device__ __forceinline__ void color_body(const JpegArgs &A, int group, int y) 
     o[2] = clamp255(Y + r);
 }
 
-__global__ __launch_bounds__(256) void jpeg_color_kernel(JpegArgs A) { color_body(A, blockIdx.x, blockIdx.y); }
+// ---------------------------------------------------------------- entries
+// One launch per kernel for all items of a decode. The item is blockIdx.y
+// (blockIdx.z for the colour kernel, whose y is the row); the entropy kernels take
+// it through the index list of their path. The item's arguments are read from a
+// device table -- the index is uniform, so these are scalar loads, as
+// kernel-argument loads are. The grid is the maximum over the items: a workgroup
+// past its own item's extent returns whole, before any barrier of the body (with
+// one item the grid is that item's extent).
 
-// ---------------------------------------------------------------- batch entries
-// psn_jpeg_decode_batch_device: one launch per kernel for all items. The item is
-// blockIdx.y (blockIdx.z for the colour kernel, whose y is the row); the entropy
-// kernels take it through the index list of their path. The item's arguments are
-// read from a device table -- the index is uniform, so these are scalar loads, as
-// the single-image entries' kernel-argument loads are. The grid is the maximum
-// over the items: a workgroup past its own item's extent returns whole, before any
-// barrier of the body.
-
-__global__ __launch_bounds__(64) void jpeg_entropy_batch_kernel(const JpegArgs *__restrict__ tab, const int *__restrict__ list) {
+__global__ __launch_bounds__(64) void jpeg_entropy_kernel(const JpegArgs *__restrict__ tab, const int *__restrict__ list) {
     const JpegArgs &A = tab[list[blockIdx.y]];
     if ((int)blockIdx.x >= (A.nseg + 63) / 64) return;
     entropy_body(A, blockIdx.x);
 }
 
-__global__ __launch_bounds__(256) void jpeg_sync_batch_kernel(const EntArgs *__restrict__ tab, const int *__restrict__ list) {
+__global__ __launch_bounds__(256) void jpeg_sync_kernel(const EntArgs *__restrict__ tab, const int *__restrict__ list) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const EntArgs &E = tab[list[blockIdx.y]];
     if ((int)blockIdx.x >= E.nseq) return;
     sync_body(E, blockIdx.x, smem);
 }
 
-__global__ __launch_bounds__(1024) void jpeg_chain_batch_kernel(const EntArgs *__restrict__ tab, const int *__restrict__ list) {
+__global__ __launch_bounds__(1024) void jpeg_chain_kernel(const EntArgs *__restrict__ tab, const int *__restrict__ list) {
     chain_body(tab[list[blockIdx.y]]);  // one workgroup per item
 }
 
-__global__ __launch_bounds__(256) void jpeg_emit_batch_kernel(const EntArgs *__restrict__ tab, const int *__restrict__ list) {
+__global__ __launch_bounds__(256) void jpeg_emit_kernel(const EntArgs *__restrict__ tab, const int *__restrict__ list) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const EntArgs &E = tab[list[blockIdx.y]];
     if ((int)blockIdx.x >= E.nseq) return;
     emit_body(E, blockIdx.x, smem);
 }
 
-__global__ __launch_bounds__(1024) void jpeg_dc_batch_kernel(const EntArgs *__restrict__ tab, const int *__restrict__ list) {
+__global__ __launch_bounds__(1024) void jpeg_dc_kernel(const EntArgs *__restrict__ tab, const int *__restrict__ list) {
     const EntArgs &E = tab[list[blockIdx.y]];
     if ((int)blockIdx.x >= E.geo.nc) return;
     dc_body(E, blockIdx.x);  // one workgroup per item and component
 }
 
-__global__ __launch_bounds__(256) void jpeg_idct_batch_kernel(const JpegArgs *__restrict__ tab) {
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const JpegArgs *__restrict__ tab) {
     const JpegArgs &A = tab[blockIdx.y];
     if ((int)blockIdx.x >= (A.nblocks + 255) / 256) return;
     idct_body(A, blockIdx.x);
 }
 
-__global__ __launch_bounds__(256) void jpeg_color_batch_kernel(const JpegArgs *__restrict__ tab) {
+__global__ __launch_bounds__(256) void jpeg_color_kernel(const JpegArgs *__restrict__ tab) {
     const JpegArgs &A = tab[blockIdx.z];
     if ((int)blockIdx.x >= (A.W + 255) / 256 || (int)blockIdx.y >= A.H) return;
     color_body(A, blockIdx.x, blockIdx.y);
@@ -590,29 +571,26 @@ __global__ __launch_bounds__(256) void jpeg_color_batch_kernel(const JpegArgs *_
 struct psn_jpeg_ctx {
     int device = 0;
     hipStream_t own = nullptr, stream = nullptr;
-    uint8_t *d_blob = nullptr, *h_blob = nullptr;  // [Tables | segment offsets | entropy bytes]
+    uint8_t *d_blob = nullptr, *h_blob = nullptr;  // the staging blob (psn::plan_batch lays it out)
     size_t blob_cap = 0;
     int16_t *d_coef = nullptr;
     size_t coef_cap = 0;
     uint8_t *d_planes = nullptr;
     size_t planes_cap = 0;
-    hipEvent_t blob_free = nullptr;  // the previous frame's kernels have read the staging blob
+    hipEvent_t blob_free = nullptr;  // the previous decode's H2D has read the staging blob
     bool blob_pending = false;
     uint8_t *d_out = nullptr;  // psn_jpeg_decode's device BGR buffer
     size_t out_cap = 0;
     int ent_mode = 0, ent_sub = 0;  // psn_jpeg_debug_set_entropy
-    uint8_t *d_par = nullptr;       // parallel path: [DevStats | states | counts | prefix sums | rounds]
+    uint8_t *d_par = nullptr;       // per item: [DevStats | states | counts | prefix sums | rounds]
     size_t par_cap = 0;
-    psn_jpeg_stats last{};          // the last decode (host part; the kernels' counters are in d_par)
-    bool decoded = false;
-    int last_nblocks = 0;           // coefficient blocks of the last decode (psn_jpeg_debug_read_coefficients)
-    size_t last_stats_off = 0, last_coef_off = 0;  // its DevStats in d_par, its coefficients in d_coef (bytes)
-    struct BatchItem {              // psn_jpeg_batch_stats, psn_jpeg_debug_read_batch_coefficients
-        psn_jpeg_stats st;
+    struct BatchItem {              // one item of the last decode (the stats and coefficient readers)
+        psn_jpeg_stats st;          // host part; a parallel item's counters are its DevStats in d_par
         int nblocks;
-        size_t stats_off, coef_off;
+        size_t stats_off, coef_off;  // its DevStats in d_par, its coefficients in d_coef (bytes)
     };
-    std::vector<BatchItem> batch;   // the items of the last decode when it was a batch; else empty
+    std::vector<BatchItem> items;    // the last decode; empty: nothing decoded yet
+    bool batch = false;             // it came in through psn_jpeg_decode_batch_device
     std::string err;
 };
 
@@ -656,6 +634,108 @@ int grow(psn_jpeg_ctx *c, T *&buf, size_t &cap, size_t need, size_t to, T **pinn
 
 namespace jent = psn::jent;
 
+// The one decode: psn_jpeg_decode_batch_device's items, or psn_jpeg_decode_device's
+// image as a batch of one (`batch` false: its errors name no item).
+int decode_items(psn_jpeg_ctx *c, const psn_jpeg_item *items, int n, bool batch) {
+    psn::Batch B;
+    std::string why;
+    int rc = psn::plan_batch(items, n, c->ent_mode, c->ent_sub, B, why);  // every item, before anything is enqueued
+    if (rc && batch && B.L.bad_item >= 0) return jerr(c, rc, "item %d: %s", B.L.bad_item, why.c_str());
+    if (rc) return jerr(c, rc, "%s", why.c_str());
+    const psn_jpeg_batch_layout &L = B.L;
+    JCHK(c, hipSetDevice(c->device));
+    if (c->blob_pending) {  // the staging blob is reused: the previous decode's H2D must be done
+        JCHK(c, hipEventSynchronize(c->blob_free));
+        c->blob_pending = false;
+    }
+    if ((rc = grow(c, c->d_blob, c->blob_cap, L.blob_size, L.blob_size + L.blob_size / 2, &c->h_blob))) return rc;
+    if ((rc = grow(c, c->d_coef, c->coef_cap, L.coef_size, L.coef_size))) return rc;
+    if ((rc = grow(c, c->d_planes, c->planes_cap, L.planes_size, L.planes_size))) return rc;
+    if ((rc = grow(c, c->d_par, c->par_cap, L.scratch_size, L.scratch_size + L.scratch_size / 2))) return rc;
+    psn::EntArgs *he = (psn::EntArgs *)(c->h_blob + L.ent_args);
+    psn::JpegArgs *ha = (psn::JpegArgs *)(c->h_blob + L.jpeg_args);
+    int *hl = (int *)(c->h_blob + L.lists);
+    std::vector<psn_jpeg_ctx::BatchItem> rec((size_t)n);
+    int sub = 0;  // the parallel items' subsequence size: one per context
+    for (int i = 0; i < n; i++) {
+        const psn::Parsed &P = B.P[(size_t)i];
+        const psn_jpeg_batch_item_layout &it = L.item[i];
+        const psn_jpeg_plan &pl = B.plans[(size_t)i];
+        memcpy(c->h_blob + it.tables, &P.tab, sizeof(psn::Tables));
+        memcpy(c->h_blob + it.segments, P.seg.data(), 4 * P.seg.size());
+        memcpy(c->h_blob + it.bytes, items[i].data + P.ent0, (size_t)P.a.data_len);
+        memset(c->h_blob + it.bytes + P.a.data_len, 0, it.bytes_size - (size_t)P.a.data_len);  // the item's slack
+        psn::batch_args(B, i, items[i], c->d_blob, c->d_par, (uint8_t *)c->d_coef, c->d_planes, ha[i], he[i]);
+        rec[(size_t)i] = {psn_jpeg_stats{pl.path, pl.segments, pl.sub_bytes, pl.subsequences, pl.sequences, 0, 0,
+                                         pl.path == PSN_JPEG_PATH_PARALLEL ? 0 : P.a.nblocks},
+                          P.a.nblocks, it.stats, it.coef};
+        if (pl.path == PSN_JPEG_PATH_PARALLEL) sub = pl.sub_bytes;
+    }
+    for (int k = 0; k < L.n_parallel; k++) hl[k] = L.parallel[k];
+    for (int k = 0; k < L.n_serial; k++) hl[n + k] = L.serial[k];
+    JCHK(c, hipMemcpyAsync(c->d_blob, c->h_blob, L.blob_size, hipMemcpyHostToDevice, c->stream));
+    JCHK(c, hipEventRecord(c->blob_free, c->stream));
+    c->blob_pending = true;
+    JCHK(c, hipMemsetAsync(c->d_coef, 0, L.coef_size, c->stream));
+    c->items = rec;  // a call refused above left the records of the last decode as they were
+    c->batch = batch;
+    const psn::EntArgs *de = (const psn::EntArgs *)(c->d_blob + L.ent_args);
+    const psn::JpegArgs *da = (const psn::JpegArgs *)(c->d_blob + L.jpeg_args);
+    const int *dl = (const int *)(c->d_blob + L.lists);
+    if (L.n_parallel) {
+        const size_t staged = sub <= PSN_JPEG_STAGE_MAX_SUB ? (size_t)jent::kSeqLen * sub + psn::kStageSlack : 0;
+        const size_t lds_sync = sizeof(psn::LdsTabs) + jent::kSeqLen * 8 + staged, lds_emit = sizeof(psn::LdsTabs) + psn::kNaturalLds + staged;
+        const dim3 seqs(L.max_sequences, L.n_parallel);
+        hipLaunchKernelGGL(psn::jpeg_sync_kernel, seqs, dim3(jent::kSeqLen), lds_sync, c->stream, de, dl);
+        JCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(psn::jpeg_chain_kernel, dim3(1, L.n_parallel), dim3(1024), 0, c->stream, de, dl);
+        JCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(psn::jpeg_emit_kernel, seqs, dim3(jent::kSeqLen), lds_emit, c->stream, de, dl);
+        JCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(psn::jpeg_dc_kernel, dim3(L.max_parallel_components, L.n_parallel), dim3(1024), 0, c->stream, de, dl);
+        JCHK(c, hipGetLastError());
+    }
+    if (L.n_serial) {
+        hipLaunchKernelGGL(psn::jpeg_entropy_kernel, dim3(L.max_segment_groups, L.n_serial), dim3(64), 0, c->stream, da, dl + n);
+        JCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(psn::jpeg_idct_kernel, dim3(L.max_block_groups, n), dim3(256), 0, c->stream, da);
+    JCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(psn::jpeg_color_kernel, dim3((L.max_width + 255) / 256, L.max_height, n), dim3(256), 0, c->stream, da);
+    JCHK(c, hipGetLastError());
+    return PSN_LK_OK;
+}
+
+// Item `item` of the last decode where that was a batch; else null, the reason in the context.
+const psn_jpeg_ctx::BatchItem *batch_item(psn_jpeg_ctx *c, int item) {
+    const size_t n = c->batch ? c->items.size() : 0;
+    if (item >= 0 && (size_t)item < n) return &c->items[(size_t)item];
+    jerr(c, PSN_LK_ERR_ARG, "item %d: the last decode was %s", item, n ? "a smaller batch" : "not a batch");
+    return nullptr;
+}
+
+int item_stats(psn_jpeg_ctx *c, const psn_jpeg_ctx::BatchItem &b, psn_jpeg_stats *out) {
+    JCHK(c, hipSetDevice(c->device));
+    JCHK(c, hipStreamSynchronize(c->stream));
+    *out = b.st;
+    if (b.st.path == PSN_JPEG_PATH_PARALLEL) {
+        psn::DevStats d;
+        JCHK(c, hipMemcpy(&d, c->d_par + b.stats_off, sizeof d, hipMemcpyDeviceToHost));
+        out->sync_rounds = d.sync_rounds;
+        out->chain_rounds = d.chain_rounds;
+        out->blocks = d.blocks;
+    }
+    return PSN_LK_OK;
+}
+
+int item_coefficients(psn_jpeg_ctx *c, const psn_jpeg_ctx::BatchItem &b, int16_t *out, size_t count) {
+    if (count != (size_t)b.nblocks * 64) return jerr(c, PSN_LK_ERR_ARG, "count %zu is not %d blocks * 64", count, b.nblocks);
+    JCHK(c, hipSetDevice(c->device));
+    JCHK(c, hipMemcpyAsync(out, (const uint8_t *)c->d_coef + b.coef_off, count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    JCHK(c, hipStreamSynchronize(c->stream));
+    return PSN_LK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -698,91 +778,8 @@ int psn_jpeg_set_stream(psn_jpeg_ctx *c, void *s) {
 
 int psn_jpeg_decode_device(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uint8_t *d_bgr, int stride) {
     if (!c || !data || !d_bgr) return PSN_LK_ERR_ARG;
-    psn::Parsed P;
-    std::string why;
-    int rc = psn::parse(data, len, P, why);
-    if (rc) return jerr(c, rc, "%s", why.c_str());
-    psn::JpegArgs &a = P.a;
-    if (stride < 3 * a.W) return jerr(c, PSN_LK_ERR_ARG, "stride %d < 3 * width %d", stride, a.W);
-    JCHK(c, hipSetDevice(c->device));
-    const size_t off_seg = (sizeof(psn::Tables) + 15) & ~(size_t)15;
-    const size_t off_data = (off_seg + 4 * P.seg.size() + 15) & ~(size_t)15;
-    const size_t blob = off_data + (size_t)a.data_len + 16;
-    if (c->blob_pending) {  // the staging blob is reused: the previous frame's H2D must be done
-        JCHK(c, hipEventSynchronize(c->blob_free));
-        c->blob_pending = false;
-    }
-    if ((rc = grow(c, c->d_blob, c->blob_cap, blob, blob + blob / 2, &c->h_blob))) return rc;
-    const size_t coef = (size_t)a.nblocks * 64 * sizeof(int16_t), planes = (size_t)a.nblocks * 64;
-    if ((rc = grow(c, c->d_coef, c->coef_cap, coef, coef))) return rc;
-    if ((rc = grow(c, c->d_planes, c->planes_cap, planes, planes))) return rc;
-    memcpy(c->h_blob, &P.tab, sizeof(psn::Tables));
-    memcpy(c->h_blob + off_seg, P.seg.data(), 4 * P.seg.size());
-    memcpy(c->h_blob + off_data, data + P.ent0, (size_t)a.data_len);
-    JCHK(c, hipMemcpyAsync(c->d_blob, c->h_blob, blob, hipMemcpyHostToDevice, c->stream));
-    JCHK(c, hipEventRecord(c->blob_free, c->stream));
-    c->blob_pending = true;
-    JCHK(c, hipMemsetAsync(c->d_coef, 0, coef, c->stream));
-    a.tab = (const psn::Tables *)c->d_blob;
-    a.seg = (const int *)(c->d_blob + off_seg);
-    a.data = c->d_blob + off_data;
-    a.coef = c->d_coef;
-    a.planes = c->d_planes;
-    a.out = d_bgr;
-    a.out_stride = stride;
-    psn_jpeg_plan pl;
-    psn::plan_entropy(P, c->ent_mode, c->ent_sub, pl);
-    c->last = psn_jpeg_stats{pl.path, pl.segments, pl.sub_bytes, pl.subsequences, pl.sequences, 0, 0, 0};
-    c->decoded = true;
-    c->last_nblocks = a.nblocks;
-    c->last_stats_off = c->last_coef_off = 0;
-    c->batch.clear();
-    if (pl.path == PSN_JPEG_PATH_PARALLEL) {
-        const size_t nsub = (size_t)pl.subsequences, nseq = (size_t)pl.sequences;
-        auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-        const size_t off_st = up16(sizeof(psn::DevStats)), off_cnt = off_st + up16(8 * nsub), off_pre = off_cnt + up16(4 * nsub),
-                     off_rounds = off_pre + up16(4 * nsub), par = off_rounds + up16(4 * nseq);
-        if ((rc = grow(c, c->d_par, c->par_cap, par, par + par / 2))) return rc;
-        psn::EntArgs e{};
-        e.tab = a.tab;
-        e.data = a.data;
-        e.len = a.data_len;
-        e.S = pl.sub_bytes;
-        e.nsub = pl.subsequences;
-        e.nseq = pl.sequences;
-        e.stage = pl.sub_bytes <= PSN_JPEG_STAGE_MAX_SUB ? 1 : 0;
-        psn::entropy_geometry(P, e.geo, e.nb0, e.bpm);
-        e.nmcu = a.nmcu;
-        for (int i = 0; i < a.nc; i++) {
-            e.td[i] = a.c[i].td;
-            e.ta[i] = a.c[i].ta;
-        }
-        e.stats = (psn::DevStats *)c->d_par;
-        e.st = (unsigned long long *)(c->d_par + off_st);
-        e.cnt = (unsigned *)(c->d_par + off_cnt);
-        e.pre = (unsigned *)(c->d_par + off_pre);
-        e.seq_rounds = (int *)(c->d_par + off_rounds);
-        e.coef = a.coef;
-        const size_t staged = e.stage ? (size_t)jent::kSeqLen * e.S + psn::kStageSlack : 0;
-        const size_t lds_sync = sizeof(psn::LdsTabs) + jent::kSeqLen * 8 + staged, lds_emit = sizeof(psn::LdsTabs) + psn::kNaturalLds + staged;
-        hipLaunchKernelGGL(psn::jpeg_sync_kernel, dim3(e.nseq), dim3(jent::kSeqLen), lds_sync, c->stream, e);
-        JCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(psn::jpeg_chain_kernel, dim3(1), dim3(1024), 0, c->stream, e);
-        JCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(psn::jpeg_emit_kernel, dim3(e.nseq), dim3(jent::kSeqLen), lds_emit, c->stream, e);
-        JCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(psn::jpeg_dc_kernel, dim3(a.nc), dim3(1024), 0, c->stream, e);
-        JCHK(c, hipGetLastError());
-    } else {
-        c->last.blocks = a.nblocks;  // the serial kernel decodes every block of the scan
-        hipLaunchKernelGGL(psn::jpeg_entropy_kernel, dim3((a.nseg + 63) / 64), dim3(64), 0, c->stream, a);
-        JCHK(c, hipGetLastError());
-    }
-    hipLaunchKernelGGL(psn::jpeg_idct_kernel, dim3((a.nblocks + 255) / 256), dim3(256), 0, c->stream, a);
-    JCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(psn::jpeg_color_kernel, dim3((a.W + 255) / 256, a.H), dim3(256), 0, c->stream, a);
-    JCHK(c, hipGetLastError());
-    return PSN_LK_OK;
+    const psn_jpeg_item item{data, len, d_bgr, stride};
+    return decode_items(c, &item, 1, false);
 }
 
 int psn_jpeg_decode(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uint8_t *bgr, int stride) {
@@ -803,106 +800,19 @@ int psn_jpeg_decode(psn_jpeg_ctx *c, const uint8_t *data, size_t len, uint8_t *b
 
 int psn_jpeg_decode_batch_device(psn_jpeg_ctx *c, const psn_jpeg_item *items, int n) {
     if (!c) return PSN_LK_ERR_ARG;
-    psn::Batch B;
-    std::string why;
-    int rc = psn::plan_batch(items, n, c->ent_mode, c->ent_sub, B, why);  // every item, before anything is enqueued
-    if (rc) return jerr(c, rc, "%s", why.c_str());
-    const psn_jpeg_batch_layout &L = B.L;
-    JCHK(c, hipSetDevice(c->device));
-    if (c->blob_pending) {  // the staging blob is reused: the previous decode's H2D must be done
-        JCHK(c, hipEventSynchronize(c->blob_free));
-        c->blob_pending = false;
-    }
-    if ((rc = grow(c, c->d_blob, c->blob_cap, L.blob_size, L.blob_size + L.blob_size / 2, &c->h_blob))) return rc;
-    if ((rc = grow(c, c->d_coef, c->coef_cap, L.coef_size, L.coef_size))) return rc;
-    if ((rc = grow(c, c->d_planes, c->planes_cap, L.planes_size, L.planes_size))) return rc;
-    if ((rc = grow(c, c->d_par, c->par_cap, L.scratch_size, L.scratch_size + L.scratch_size / 2))) return rc;
-    psn::EntArgs *he = (psn::EntArgs *)(c->h_blob + L.ent_args);
-    psn::JpegArgs *ha = (psn::JpegArgs *)(c->h_blob + L.jpeg_args);
-    int *hl = (int *)(c->h_blob + L.lists);
-    std::vector<psn_jpeg_ctx::BatchItem> rec((size_t)n);
-    int sub = 0;  // the parallel items' subsequence size: one per context
-    for (int i = 0; i < n; i++) {
-        const psn::Parsed &P = B.P[(size_t)i];
-        const psn_jpeg_batch_item_layout &it = L.item[i];
-        const psn_jpeg_plan &pl = B.plans[(size_t)i];
-        memcpy(c->h_blob + it.tables, &P.tab, sizeof(psn::Tables));
-        memcpy(c->h_blob + it.segments, P.seg.data(), 4 * P.seg.size());
-        memcpy(c->h_blob + it.bytes, items[i].data + P.ent0, (size_t)P.a.data_len);
-        memset(c->h_blob + it.bytes + P.a.data_len, 0, it.bytes_size - (size_t)P.a.data_len);  // the item's slack
-        psn::batch_args(B, i, items[i], c->d_blob, c->d_par, (uint8_t *)c->d_coef, c->d_planes, ha[i], he[i]);
-        rec[(size_t)i] = {psn_jpeg_stats{pl.path, pl.segments, pl.sub_bytes, pl.subsequences, pl.sequences, 0, 0,
-                                         pl.path == PSN_JPEG_PATH_PARALLEL ? 0 : P.a.nblocks},
-                          P.a.nblocks, it.stats, it.coef};
-        if (pl.path == PSN_JPEG_PATH_PARALLEL) sub = pl.sub_bytes;
-    }
-    for (int k = 0; k < L.n_parallel; k++) hl[k] = L.parallel[k];
-    for (int k = 0; k < L.n_serial; k++) hl[n + k] = L.serial[k];
-    JCHK(c, hipMemcpyAsync(c->d_blob, c->h_blob, L.blob_size, hipMemcpyHostToDevice, c->stream));
-    JCHK(c, hipEventRecord(c->blob_free, c->stream));
-    c->blob_pending = true;
-    JCHK(c, hipMemsetAsync(c->d_coef, 0, L.coef_size, c->stream));
-    c->batch = rec;
-    c->last = rec.back().st;
-    c->decoded = true;
-    c->last_nblocks = rec.back().nblocks;
-    c->last_stats_off = rec.back().stats_off;
-    c->last_coef_off = rec.back().coef_off;
-    const psn::EntArgs *de = (const psn::EntArgs *)(c->d_blob + L.ent_args);
-    const psn::JpegArgs *da = (const psn::JpegArgs *)(c->d_blob + L.jpeg_args);
-    const int *dl = (const int *)(c->d_blob + L.lists);
-    if (L.n_parallel) {
-        const size_t staged = sub <= PSN_JPEG_STAGE_MAX_SUB ? (size_t)jent::kSeqLen * sub + psn::kStageSlack : 0;
-        const size_t lds_sync = sizeof(psn::LdsTabs) + jent::kSeqLen * 8 + staged, lds_emit = sizeof(psn::LdsTabs) + psn::kNaturalLds + staged;
-        const dim3 seqs(L.max_sequences, L.n_parallel);
-        hipLaunchKernelGGL(psn::jpeg_sync_batch_kernel, seqs, dim3(jent::kSeqLen), lds_sync, c->stream, de, dl);
-        JCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(psn::jpeg_chain_batch_kernel, dim3(1, L.n_parallel), dim3(1024), 0, c->stream, de, dl);
-        JCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(psn::jpeg_emit_batch_kernel, seqs, dim3(jent::kSeqLen), lds_emit, c->stream, de, dl);
-        JCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(psn::jpeg_dc_batch_kernel, dim3(L.max_parallel_components, L.n_parallel), dim3(1024), 0, c->stream, de, dl);
-        JCHK(c, hipGetLastError());
-    }
-    if (L.n_serial) {
-        hipLaunchKernelGGL(psn::jpeg_entropy_batch_kernel, dim3(L.max_segment_groups, L.n_serial), dim3(64), 0, c->stream, da, dl + n);
-        JCHK(c, hipGetLastError());
-    }
-    hipLaunchKernelGGL(psn::jpeg_idct_batch_kernel, dim3(L.max_block_groups, n), dim3(256), 0, c->stream, da);
-    JCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(psn::jpeg_color_batch_kernel, dim3((L.max_width + 255) / 256, L.max_height, n), dim3(256), 0, c->stream, da);
-    JCHK(c, hipGetLastError());
-    return PSN_LK_OK;
+    return decode_items(c, items, n, true);
 }
 
 int psn_jpeg_batch_stats(psn_jpeg_ctx *c, int item, psn_jpeg_stats *out) {
     if (!c || !out) return PSN_LK_ERR_ARG;
-    if (item < 0 || (size_t)item >= c->batch.size())
-        return jerr(c, PSN_LK_ERR_ARG, "item %d: the last decode was %s", item, c->batch.empty() ? "not a batch" : "a smaller batch");
-    JCHK(c, hipSetDevice(c->device));
-    JCHK(c, hipStreamSynchronize(c->stream));
-    const psn_jpeg_ctx::BatchItem &b = c->batch[(size_t)item];
-    *out = b.st;
-    if (b.st.path == PSN_JPEG_PATH_PARALLEL) {
-        psn::DevStats d;
-        JCHK(c, hipMemcpy(&d, c->d_par + b.stats_off, sizeof d, hipMemcpyDeviceToHost));
-        out->sync_rounds = d.sync_rounds;
-        out->chain_rounds = d.chain_rounds;
-        out->blocks = d.blocks;
-    }
-    return PSN_LK_OK;
+    const psn_jpeg_ctx::BatchItem *b = batch_item(c, item);
+    return b ? item_stats(c, *b, out) : PSN_LK_ERR_ARG;
 }
 
 int psn_jpeg_debug_read_batch_coefficients(psn_jpeg_ctx *c, int item, int16_t *out, size_t count) {
     if (!c || !out) return PSN_LK_ERR_ARG;
-    if (item < 0 || (size_t)item >= c->batch.size())
-        return jerr(c, PSN_LK_ERR_ARG, "item %d: the last decode was %s", item, c->batch.empty() ? "not a batch" : "a smaller batch");
-    const psn_jpeg_ctx::BatchItem &b = c->batch[(size_t)item];
-    if (count != (size_t)b.nblocks * 64) return jerr(c, PSN_LK_ERR_ARG, "count %zu is not %d blocks * 64", count, b.nblocks);
-    JCHK(c, hipSetDevice(c->device));
-    JCHK(c, hipMemcpyAsync(out, (const uint8_t *)c->d_coef + b.coef_off, count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
-    JCHK(c, hipStreamSynchronize(c->stream));
-    return PSN_LK_OK;
+    const psn_jpeg_ctx::BatchItem *b = batch_item(c, item);
+    return b ? item_coefficients(c, *b, out, count) : PSN_LK_ERR_ARG;
 }
 
 int psn_jpeg_debug_set_entropy(psn_jpeg_ctx *c, int mode, int sub_bytes) {
@@ -916,29 +826,14 @@ int psn_jpeg_debug_set_entropy(psn_jpeg_ctx *c, int mode, int sub_bytes) {
 
 int psn_jpeg_debug_read_coefficients(psn_jpeg_ctx *c, int16_t *out, size_t count) {
     if (!c || !out) return PSN_LK_ERR_ARG;
-    if (!c->decoded) return jerr(c, PSN_LK_ERR_ARG, "nothing decoded yet");
-    if (count != (size_t)c->last_nblocks * 64)
-        return jerr(c, PSN_LK_ERR_ARG, "count %zu is not %d blocks * 64", count, c->last_nblocks);
-    JCHK(c, hipSetDevice(c->device));
-    JCHK(c, hipMemcpyAsync(out, (const uint8_t *)c->d_coef + c->last_coef_off, count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
-    JCHK(c, hipStreamSynchronize(c->stream));
-    return PSN_LK_OK;
+    if (c->items.empty()) return jerr(c, PSN_LK_ERR_ARG, "nothing decoded yet");
+    return item_coefficients(c, c->items.back(), out, count);
 }
 
 int psn_jpeg_last_stats(psn_jpeg_ctx *c, psn_jpeg_stats *out) {
     if (!c || !out) return PSN_LK_ERR_ARG;
-    if (!c->decoded) return jerr(c, PSN_LK_ERR_ARG, "nothing decoded yet");
-    JCHK(c, hipSetDevice(c->device));
-    JCHK(c, hipStreamSynchronize(c->stream));
-    *out = c->last;
-    if (c->last.path == PSN_JPEG_PATH_PARALLEL) {
-        psn::DevStats d;
-        JCHK(c, hipMemcpy(&d, c->d_par + c->last_stats_off, sizeof d, hipMemcpyDeviceToHost));
-        out->sync_rounds = d.sync_rounds;
-        out->chain_rounds = d.chain_rounds;
-        out->blocks = d.blocks;
-    }
-    return PSN_LK_OK;
+    if (c->items.empty()) return jerr(c, PSN_LK_ERR_ARG, "nothing decoded yet");
+    return item_stats(c, c->items.back(), out);
 }
 
 }  // extern "C"

@@ -223,14 +223,12 @@ int plan_batch(const psn_jpeg_item *items, int n, int mode, int sub, Batch &B, s
     B.P.assign((size_t)n, Parsed());
     B.plans.assign((size_t)n, psn_jpeg_plan());
     for (int i = 0; i < n; i++) {  // every item is checked before anything is laid out
-        const std::string at = "item " + std::to_string(i) + ": ";
         L.bad_item = i;
-        if (!items[i].data || !items[i].d_bgr) return why = at + "null pointer", PSN_LK_ERR_ARG;
-        std::string w;
-        const int rc = parse(items[i].data, items[i].len, B.P[(size_t)i], w);
-        if (rc) return why = at + w, rc;
+        if (!items[i].data || !items[i].d_bgr) return why = "null pointer", PSN_LK_ERR_ARG;
+        const int rc = parse(items[i].data, items[i].len, B.P[(size_t)i], why);
+        if (rc) return rc;
         if (items[i].stride < 3 * B.P[(size_t)i].a.W)
-            return why = at + "stride " + std::to_string(items[i].stride) + " < 3 * width " + std::to_string(B.P[(size_t)i].a.W),
+            return why = "stride " + std::to_string(items[i].stride) + " < 3 * width " + std::to_string(B.P[(size_t)i].a.W),
                    PSN_LK_ERR_ARG;
         plan_entropy(B.P[(size_t)i], mode, sub, B.plans[(size_t)i]);
     }

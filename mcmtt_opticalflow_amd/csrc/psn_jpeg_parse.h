@@ -115,8 +115,9 @@ void plan_entropy(const Parsed &P, int mode, int sub, psn_jpeg_plan &pl);
 // The scan's block layout as the symbol step's sinks address it.
 void entropy_geometry(const Parsed &P, jent::Geo &G, int &nb0, int &bpm);
 
-// A batch (psn_jpeg_decode_batch_device): the parsed items, their plans and where
-// each item's tables, bytes, scratch, coefficients and planes lie.
+// A batch (psn_jpeg_decode_batch_device; psn_jpeg_decode_device's image is a batch
+// of one): the parsed items, their plans and where each item's tables, bytes,
+// scratch, coefficients and planes lie.
 struct Batch {
     std::vector<Parsed> P;
     std::vector<psn_jpeg_plan> plans;
@@ -125,7 +126,8 @@ struct Batch {
 
 // Checks and parses every item, plans it (mode, sub: psn_jpeg_debug_set_entropy)
 // and lays the batch out. On an error B.L.bad_item is the first bad item (-1: the
-// call's own arguments) and `why` names it.
+// call's own arguments) and `why` the bare reason: the caller that has items to
+// speak of names the item.
 int plan_batch(const psn_jpeg_item *items, int n, int mode, int sub, Batch &B, std::string &why);
 
 // The kernels' arguments of item i of a planned batch, over the base addresses of

@@ -641,30 +641,48 @@ static int ensure_stage(psn_lk_ctx *c, int slot, size_t need) {
     return PSN_LK_OK;
 }
 
-int psn_lk_push_frame_jpeg(psn_lk_ctx *c, int slot, const uint8_t *jpeg, size_t len) {
-    if (!c || !jpeg) return PSN_LK_ERR_ARG;
-    if (check_user_slot(c, slot)) return PSN_LK_ERR_SLOT;
-    int w = 0, h = 0;
-    int rc = psn_jpeg_info(jpeg, len, &w, &h, nullptr);
-    if (rc) return set_err(c, rc, "JPEG headers");
-    if (w != c->src_w || h != c->src_h) return set_err(c, PSN_LK_ERR_ARG, "JPEG %dx%d, context %dx%d", w, h, c->src_w, c->src_h);
+// Decodes n checked frames into their slots' staging buffers in one device pass
+// and builds the slots' pyramids. `batch`: through psn_jpeg_decode_batch_device
+// (psn_lk_jpeg_batch_stats speaks of a batch only).
+static int push_jpeg(psn_lk_ctx *c, const int *slots, const uint8_t *const *jpeg, const size_t *len, int n, bool batch) {
     HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = flush_pending(c))) return rc;
+    int rc = flush_pending(c);
+    if (rc) return rc;
     if (!c->jpeg) {
         if ((rc = psn_jpeg_create(c->device, &c->jpeg))) return set_err(c, rc, "psn_jpeg_create");
         psn_jpeg_set_stream(c->jpeg, c->ingest_stream);
     }
     const size_t row = (size_t)c->src_w * 3;
-    if ((rc = ensure_stage(c, slot, row * c->src_h))) return rc;
-    if ((rc = c->slots.wait_free(slot, c->ingest_stream))) return rc;
-    // the slot's previous build may still read d_stage[slot] (an async push builds
-    // on either ingest stream): the decode overwrites it only after that build
-    if ((rc = c->slots.wait_prev_build(slot, c->ingest_stream))) return rc;
-    rc = psn_jpeg_decode_device(c->jpeg, jpeg, len, c->d_stage[slot], (int)row);
+    for (int i = 0; i < n; i++)
+        if ((rc = ensure_stage(c, slots[i], row * c->src_h))) return rc;
+    psn_jpeg_item items[PSN_JPEG_MAX_BATCH];
+    for (int i = 0; i < n; i++) {
+        if ((rc = c->slots.wait_free(slots[i], c->ingest_stream))) return rc;
+        // the slot's previous build may still read d_stage[slot] (an async push builds
+        // on either ingest stream): the decode overwrites it only after that build
+        if ((rc = c->slots.wait_prev_build(slots[i], c->ingest_stream))) return rc;
+        items[i] = {jpeg[i], len[i], c->d_stage[slots[i]], (int)row};
+    }
+    rc = batch ? psn_jpeg_decode_batch_device(c->jpeg, items, n)
+               : psn_jpeg_decode_device(c->jpeg, items[0].data, items[0].len, items[0].d_bgr, items[0].stride);
     if (rc) return set_err(c, rc, "JPEG decode: %s", psn_jpeg_last_error(c->jpeg));
-    c->filled[slot] = 1;
-    c->color_src[slot] = {c->d_stage[slot], (int)row, 3, false, 0};
-    return ingest_build(c, slot, c->d_stage[slot], (int)row, 3, c->ingest_stream);
+    for (int i = 0; i < n; i++) {
+        const int slot = slots[i];
+        c->filled[slot] = 1;
+        c->color_src[slot] = {c->d_stage[slot], (int)row, 3, false, 0};
+        if ((rc = ingest_build(c, slot, c->d_stage[slot], (int)row, 3, c->ingest_stream))) return rc;
+    }
+    return PSN_LK_OK;
+}
+
+int psn_lk_push_frame_jpeg(psn_lk_ctx *c, int slot, const uint8_t *jpeg, size_t len) {
+    if (!c || !jpeg) return PSN_LK_ERR_ARG;
+    if (check_user_slot(c, slot)) return PSN_LK_ERR_SLOT;
+    int w = 0, h = 0;
+    const int rc = psn_jpeg_info(jpeg, len, &w, &h, nullptr);
+    if (rc) return set_err(c, rc, "JPEG headers");
+    if (w != c->src_w || h != c->src_h) return set_err(c, PSN_LK_ERR_ARG, "JPEG %dx%d, context %dx%d", w, h, c->src_w, c->src_h);
+    return push_jpeg(c, &slot, &jpeg, &len, 1, false);
 }
 
 int psn_lk_push_frames_jpeg(psn_lk_ctx *c, const int *slots, const uint8_t *const *jpeg, const size_t *len, int n) {
@@ -681,33 +699,7 @@ int psn_lk_push_frames_jpeg(psn_lk_ctx *c, const int *slots, const uint8_t *cons
         if (w != c->src_w || h != c->src_h)
             return set_err(c, PSN_LK_ERR_ARG, "item %d: JPEG %dx%d, context %dx%d", i, w, h, c->src_w, c->src_h);
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c);
-    if (rc) return rc;
-    if (!c->jpeg) {
-        if ((rc = psn_jpeg_create(c->device, &c->jpeg))) return set_err(c, rc, "psn_jpeg_create");
-        psn_jpeg_set_stream(c->jpeg, c->ingest_stream);
-    }
-    const size_t row = (size_t)c->src_w * 3;
-    for (int i = 0; i < n; i++)
-        if ((rc = ensure_stage(c, slots[i], row * c->src_h))) return rc;
-    psn_jpeg_item items[PSN_JPEG_MAX_BATCH];
-    for (int i = 0; i < n; i++) {
-        // as psn_lk_push_frame_jpeg: the decode overwrites a staging buffer only after
-        // the slot's readers and its previous build
-        if ((rc = c->slots.wait_free(slots[i], c->ingest_stream))) return rc;
-        if ((rc = c->slots.wait_prev_build(slots[i], c->ingest_stream))) return rc;
-        items[i] = {jpeg[i], len[i], c->d_stage[slots[i]], (int)row};
-    }
-    rc = psn_jpeg_decode_batch_device(c->jpeg, items, n);
-    if (rc) return set_err(c, rc, "JPEG decode: %s", psn_jpeg_last_error(c->jpeg));
-    for (int i = 0; i < n; i++) {
-        const int slot = slots[i];
-        c->filled[slot] = 1;
-        c->color_src[slot] = {c->d_stage[slot], (int)row, 3, false, 0};
-        if ((rc = ingest_build(c, slot, c->d_stage[slot], (int)row, 3, c->ingest_stream))) return rc;
-    }
-    return PSN_LK_OK;
+    return push_jpeg(c, slots, jpeg, len, n, true);
 }
 
 int psn_lk_jpeg_last_stats(psn_lk_ctx *c, struct psn_jpeg_stats *out) {

@@ -1,9 +1,11 @@
 """A frame-set's JPEG files decoded in one batched device pass
 (psn_jpeg_decode_batch_device, psn_lk_push_frames_jpeg,
-psn_t2d_group_push_frames_jpeg) against the single-image entries.
+psn_t2d_group_push_frames_jpeg) against the single-image calls.
 
-The reference of every item is never another batch: the existing single-image
-psn_jpeg_decode on a fresh decoder, the CPU oracle, PIL's decodes of the golden
+The reference of every item is never another batch: the single-image
+psn_jpeg_decode on a fresh decoder (the same device code as a batch of one: an
+item decodes the same alone and among neighbours), the CPU oracle (independent
+of the library: every item of every batch), PIL's decodes of the golden
 fixtures, and for synthesised streams the coefficient arrays they were written
 from. The cases are the smallest that reach each way a batch entry can go wrong:
 unequal extents (early-exit workgroups), per-item round counters, both entropy
@@ -34,12 +36,21 @@ def _single(data, entropy=0, sub=0):
         return out, dec.stats()
 
 
-def _check_batch(dec, files, entropy=0, sub=0, stats=True):
+@functools.lru_cache(maxsize=None)
+def _oracle(oracle_mod, data):
+    """The CPU oracle's pixels (it feeds zeros past a truncated stream, as the device readers do)."""
+    out = oracle_mod.jpeg_decode_bgr(data)
+    out.setflags(write=False)
+    return out
+
+
+def _check_batch(oracle_mod, dec, files, entropy=0, sub=0, stats=True):
     outs = dec.decode_batch(files)
     assert len(outs) == len(files)
     for i, (f, got) in enumerate(zip(files, outs)):
         ref, st = _single(f, entropy, sub)
         np.testing.assert_array_equal(got, ref, err_msg=f"item {i}")
+        np.testing.assert_array_equal(got, _oracle(oracle_mod, f), err_msg=f"item {i} against the oracle")
         if stats:
             assert dec.batch_stats(i) == st, f"item {i}"
     return outs
@@ -60,7 +71,7 @@ def test_mixed_geometry_and_path_in_one_batch(oracle_mod):
     ones (parallel list)."""
     files = [jv.fixture(n)[0] for n in FIXTURES]
     with lk.JpegDecoder() as dec:
-        outs = _check_batch(dec, files)
+        outs = _check_batch(oracle_mod, dec, files)
         paths = {dec.batch_stats(i)["path"] for i in range(len(files))}
         assert dec.stats() == dec.batch_stats(len(files) - 1)  # the last item's
     assert paths == {_lib.JPEG_PATH_SERIAL, _lib.JPEG_PATH_PARALLEL}
@@ -77,7 +88,7 @@ def test_unequal_extents_at_sub4(oracle_mod):
     amb = js.case("ambiguous444")
     files = [jv.fixture("gray_q80")[0], jv.fixture("444_q95")[0], amb.data]
     with lk.JpegDecoder(entropy=2, sub_bytes=4) as dec:
-        outs = _check_batch(dec, files, 2, 4)
+        outs = _check_batch(oracle_mod, dec, files, 2, 4)
         st = [dec.batch_stats(i) for i in range(3)]
         assert st[0]["sequences"] == 1 and st[0]["subsequences"] < 256 and st[1]["sequences"] == 8
         assert st[2]["sync_rounds"] == 256 and st[2]["chain_rounds"] == st[2]["sequences"] >= 4
@@ -104,7 +115,7 @@ def test_more_than_1024_sequences_in_one_item():
 
 
 @pytest.mark.parametrize("sub", [4, 64])
-def test_a_neighbours_bytes(sub):
+def test_a_neighbours_bytes(oracle_mod, sub):
     """A file cut at 40 % before and after intact files, ladder_ff (a third of its
     bytes FF) first and last in the blob: the emit kernel's last thread decodes
     past a truncated item's end and must read zeros there, not the next item's
@@ -113,20 +124,20 @@ def test_a_neighbours_bytes(sub):
     cut = _cut40(jv.fixture("422_q90")[0])
     files = [lad, cut, jv.fixture("420_q75")[0], cut, jv.fixture("444_q95")[0], _cut40(jv.fixture("gray_q80")[0]), lad]
     with lk.JpegDecoder(entropy=2, sub_bytes=sub) as dec:
-        fwd = _check_batch(dec, files, 2, sub)
-        rev = _check_batch(dec, files[::-1], 2, sub)
+        fwd = _check_batch(oracle_mod, dec, files, 2, sub)
+        rev = _check_batch(oracle_mod, dec, files[::-1], 2, sub)
     for a, b in zip(fwd, rev[::-1]):
         np.testing.assert_array_equal(a, b)
 
 
-def test_sizes():
+def test_sizes(oracle_mod):
     name, f = "420_tiny", jv.fixture("420_tiny")[0]
     big = jv.fixture("444_q95")[0]
     with lk.JpegDecoder() as dec:
-        _check_batch(dec, [big])                       # n = 1
-        outs = _check_batch(dec, [big] * 8)            # the same file into 8 outputs
+        _check_batch(oracle_mod, dec, [big])                       # n = 1
+        outs = _check_batch(oracle_mod, dec, [big] * 8)            # the same file into 8 outputs
         assert all(np.array_equal(o, outs[0]) for o in outs)
-        _check_batch(dec, [f] * _lib.JPEG_MAX_BATCH)   # the largest batch
+        _check_batch(oracle_mod, dec, [f] * _lib.JPEG_MAX_BATCH)   # the largest batch
         with pytest.raises(lk.PsnLkError):
             dec.batch_stats(_lib.JPEG_MAX_BATCH)
         with pytest.raises(lk.PsnLkError) as e:
@@ -134,18 +145,18 @@ def test_sizes():
         assert e.value.code == -1
 
 
-def test_all_or_nothing():
+def test_all_or_nothing(oracle_mod):
     good = [jv.fixture(n)[0] for n in ("420_q75", "gray_q80", "420_q85_rstrow", "444_q95")]
     bad = list(good)
     bad[2] = bad[2][:2] + b"\x00\x00" + bad[2][4:]  # no marker after SOI
     with lk.JpegDecoder() as dec:
-        _check_batch(dec, good[:2])
+        _check_batch(oracle_mod, dec, good[:2])
         before = dec.stats()
         with pytest.raises(lk.PsnLkError) as e:
             dec.decode_batch(bad)
         assert e.value.code == -1 and "item 2" in str(e.value)
         assert dec.stats() == before and dec.batch_stats(1) == before  # the context is as it was
-        _check_batch(dec, good)
+        _check_batch(oracle_mod, dec, good)
         ref, st = _single(good[0])
         np.testing.assert_array_equal(dec.decode(good[0]), ref)
         assert dec.stats() == st
@@ -154,11 +165,11 @@ def test_all_or_nothing():
 
 
 @pytest.mark.parametrize("entropy,sub", [(1, 0), (2, 4), (2, 64), (2, 256)])
-def test_modes_and_sizes(entropy, sub):
+def test_modes_and_sizes(oracle_mod, entropy, sub):
     """Debug modes 1 and 2, S in {4, 64, 256} (256: bytes unstaged)."""
     files = [jv.fixture("422_q90")[0], jv.fixture("420_q30_rst3")[0], jv.fixture("444_q95")[0]]
     with lk.JpegDecoder(entropy=entropy, sub_bytes=sub) as dec:
-        _check_batch(dec, files, entropy, sub)
+        _check_batch(oracle_mod, dec, files, entropy, sub)
         want = _lib.JPEG_PATH_SERIAL if entropy == 1 else _lib.JPEG_PATH_PARALLEL
         assert [dec.batch_stats(i)["path"] for i in range(3)] == [want, _lib.JPEG_PATH_SERIAL, want]
 

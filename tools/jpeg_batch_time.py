@@ -15,7 +15,9 @@ the enqueue.
 for n = 1, 2, 4, 8. Per-kernel times: run one child under
 `rocprofv3 --kernel-trace --stats` on its own (--only batch --n 4).
 
-usage: python tools/jpeg_batch_time.py --ab A_DIR B_DIR [--rounds 3] [--out profiles/jpeg_batch.json]
+Build A runs (a) alone unless --a-only names more (an A that has the batch call).
+
+usage: python tools/jpeg_batch_time.py --ab A_DIR B_DIR [--rounds 3] [--a-only single batch group] [--out profiles/jpeg_batch.json]
        python tools/jpeg_batch_time.py [--lib-dir DIR] [--only single batch group] [--n 1 2 4 8]
 """
 import argparse
@@ -154,7 +156,7 @@ def ab(args):
     a_dir, b_dir = args.ab
     rounds = {"A": [], "B": []}
     for r in range(args.rounds):
-        for v, d, only in (("A", a_dir, ["single"]), ("B", b_dir, ["single", "batch", "group"])):
+        for v, d, only in (("A", a_dir, args.a_only), ("B", b_dir, ["single", "batch", "group"])):
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--lib-dir", d, "--reps", str(args.reps), "--only",
                                 *only, "--n", *map(str, args.n)], capture_output=True, text=True, timeout=args.child_timeout)
             if p.returncode != 0:
@@ -201,6 +203,7 @@ def main():
     ap.add_argument("--only", nargs="+", default=["single", "batch", "group"])
     ap.add_argument("--n", nargs="+", type=int, default=list(NS))
     ap.add_argument("--ab", nargs=2, metavar=("A_DIR", "B_DIR"), default=None)
+    ap.add_argument("--a-only", nargs="+", default=["single"], help="--ab: what build A runs (an A that has the batch call: all three)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--child-timeout", type=int, default=240)
     args = ap.parse_args()

@@ -17,7 +17,7 @@ one call, and writes the per-round figures, their spread and the ratios.
 Per-kernel times: run a child under `rocprofv3 --kernel-trace --stats` on its own.
 
 usage: python tools/jpeg_time.py [--lib-dir DIR] [--reps N] [--only KEY...] [--out FILE.json]
-       python tools/jpeg_time.py --ab A_DIR B_DIR [--rounds R] [--out profiles/jpeg_entropy.json]
+       python tools/jpeg_time.py --ab A_DIR B_DIR [--rounds R] [--only KEY...] [--out profiles/jpeg_entropy.json]
 """
 import argparse
 import ctypes
@@ -152,7 +152,8 @@ def ab(args):
     rounds = {"A": [], "B": []}
     for r in range(args.rounds):
         for v, d in (("A", a_dir), ("B", b_dir)):
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--lib-dir", d, "--reps", str(args.reps)],
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--lib-dir", d, "--reps", str(args.reps),
+                                *(["--only", *args.only] if args.only else [])],
                                capture_output=True, text=True, timeout=args.child_timeout)
             if p.returncode != 0:
                 sys.stderr.write(p.stdout + p.stderr)
