@@ -29,7 +29,10 @@ extern "C" {
  *   cur      [ndet][cap][2]  input points of this step (the LK prevPts)
  *   nxt      [ndet][cap][2]  the LK nextPts of this step (every point, status ignored: :787)
  *   cnt      [ndet]          in: points of this step (0 = chain stopped);
- *                            out: inliers kept, 0 when fewer than 4 (:788)
+ *                            out: inliers kept, 0 when fewer than 4 (:788). A step needs
+ *                            cnt <= cap and relies on its two writers for it: GridFAST's select
+ *                            stores min(total, cap) and the host upload min(features, cap)
+ *                            (only chain_begin clamps a larger count, for set 0)
  *   next_in  [ndet][cap][2]  out: the inliers' nextPts = the next step's input
  *   out_boxes[ndet][steps][4] out: box pushed at step s in row s (row 0 = the host's detection box)
  *   sets     [ndet][steps][cap][2], set_cnt [ndet][steps]

@@ -3,7 +3,9 @@ the CPU restatement oracle/tracker2d_oracle.py.
 
 CPU: every header symbol is exported; PSN_Rect arithmetic, BoxMatchingCost and
 LocalSearchKLT agree with the restatement bit for bit on known answers and
-seeded random cases (static points, clusters, ties, empty input).
+seeded random cases (static points, clusters, ties, empty input). The device
+twin of LocalSearchKLT (chain_step_kernel, the one on the hot path) meets the
+same generators and the constructed edge families in test_chain_step_gpu.py.
 GPU: a multi-frame sequence -- backward chains over the 4-frame ring, forward
 tracking, matching costs, the majority gate -- through the C ABI (batched LK
 launches on the device) equals the reference schedule run on the CPU oracle
@@ -20,6 +22,8 @@ from mcmtt_opticalflow_amd import synth
 from mcmtt_opticalflow_amd import tracker2d as t2d
 
 ORC = pytest.importorskip("tracker2d_oracle")
+
+import chain_ref  # noqa: E402  (tests/chain_ref.py: the generators shared with test_chain_step_gpu.py)
 
 
 def test_symbols_exported():
@@ -62,29 +66,13 @@ def test_rect_ops_match_oracle():
         assert L.psn_rect_contain(cp, px, py) == int(p.contain(px, py))
 
 
-def _klt_case(rng, n, kind):
-    pre = rng.uniform(0, 100, (n, 2)).astype(np.float32)
-    if kind == "static":
-        d = rng.normal(0, 0.03, (n, 2))
-    elif kind == "cluster":
-        d = np.array([rng.uniform(-5, 5), rng.uniform(-5, 5)]) + rng.normal(0, 0.3, (n, 2))
-        out = rng.random(n) < 0.3
-        d[out] = rng.uniform(-20, 20, (out.sum(), 2))
-    elif kind == "ties":
-        d = rng.integers(-3, 4, (n, 2)).astype(np.float64)
-    else:
-        d = rng.uniform(-8, 8, (n, 2))
-    cur = (pre + d).astype(np.float32)
-    return pre, cur
-
-
 @pytest.mark.parametrize("kind", ["static", "cluster", "ties", "uniform"])
 def test_local_search_klt_matches_oracle(kind):
     rng = np.random.default_rng({"static": 1, "cluster": 2, "ties": 3, "uniform": 4}[kind])
     for trial in range(150):
         n = int(rng.integers(0, 101))
-        pre, cur = _klt_case(rng, n, kind)
-        box = (rng.uniform(0, 200), rng.uniform(0, 200), float(rng.integers(8, 80)), float(rng.integers(20, 200)))
+        pre, cur = chain_ref.klt_case(rng, n, kind)
+        box = chain_ref.klt_box(rng)
         g_box, g_inl = t2d.local_search_klt(box, pre, cur)
         r_box, r_inl = ORC.local_search_klt(ORC.Rect(*box), pre, cur)
         assert g_box == r_box.tuple(), (kind, trial)
@@ -97,12 +85,7 @@ def test_local_search_klt_window_edges():
     # two-pointer count of the host code must equal the restatement's double loop
     rng = np.random.default_rng(7)
     for trial in range(300):
-        n = int(rng.integers(1, 101))
-        pre = rng.uniform(0, 100, (n, 2)).astype(np.float32)
-        d = rng.integers(-4, 5, (n, 2)).astype(np.float64) * rng.choice([0.5, 1.0, 2.0])
-        cur = (pre + d).astype(np.float32)
-        w = float(rng.choice([0.0, -5.0, 5.0, 10.0, 15.0, 20.0, 25.0, 7.5, 12.5]))
-        box = (rng.uniform(0, 200), rng.uniform(0, 200), w, 40.0)
+        box, pre, cur = chain_ref.window_edge_case(rng)
         g_box, g_inl = t2d.local_search_klt(box, pre, cur)
         r_box, r_inl = ORC.local_search_klt(ORC.Rect(*box), pre, cur)
         assert g_box == r_box.tuple(), trial
