@@ -302,7 +302,8 @@ int psn_lk_timing_entries(psn_lk_ctx *ctx, int cap, int *entry, int *n);
  *                              64..512 single-tile workgroup size
  *   PSN_LK_VARIANT_GENERIC     1 = always the row-tiled kernel
  *   PSN_LK_VARIANT_ONEWAVE     0 = multi-wave iterations in the single-tile kernel
- *   PSN_LK_VARIANT_BOX         0 = box windows run the row-tiled kernel, not lk_kernel_bx
+ *   PSN_LK_VARIANT_BOX         0 = box windows run the row-tiled kernel, not lk_kernel_bx;
+ *                              2 = lk_kernel_bx also for the windows of the single-tile kernel
  *   PSN_LK_VARIANT_TILED_LDS   LDS budget (bytes) of a row-tiled workgroup
  *   PSN_LK_VARIANT_FUSED_HELPERS  tile-only workgroups per fused-ingest launch
  *   PSN_LK_VARIANT_LARGE       1 = every query runs the large-window kernel (lk_kernel_lg)

@@ -1014,7 +1014,10 @@ int psn_lk_debug_set_variant(psn_lk_ctx *c, int key, int value) {
         return PSN_LK_OK;
     case PSN_LK_VARIANT_GENERIC: c->cfg.force_generic = value != 0; return PSN_LK_OK;
     case PSN_LK_VARIANT_ONEWAVE: c->cfg.onewave = value != 0; return PSN_LK_OK;
-    case PSN_LK_VARIANT_BOX: c->cfg.box = value != 0; return PSN_LK_OK;
+    case PSN_LK_VARIANT_BOX:
+        c->cfg.box = value != 0;
+        c->cfg.box_small = value == 2;
+        return PSN_LK_OK;
     case PSN_LK_VARIANT_TILED_LDS: c->cfg.tiled_lds = std::max(16 * 1024, std::min(value, 160 * 1024 - 1024)); return PSN_LK_OK;
     case PSN_LK_VARIANT_FUSED_HELPERS: c->fused_helpers = std::max(0, value); return PSN_LK_OK;
     case PSN_LK_VARIANT_LARGE: c->cfg.force_large = value != 0; return PSN_LK_OK;

@@ -497,6 +497,70 @@ __device__ __forceinline__ float chain_sum_pl(const float *p, int len, int nbmax
     return acc;
 }
 
+// The same sum of a FULL no-tail tile (lk_kernel_fw: NB = bx_nt_tile_blocks, a
+// constant of the build) as straight-line code: every block load at an
+// immediate offset from the one base register, the two register sets
+// and the lgkmcnt(4) discipline of chain_sum_pl<true>, no loop counter, compare,
+// branch or address add between the dependent adds, and no read past the chain.
+// PSN_BX_CHAIN_NT=0 compiles the loops of chain_sum_pl everywhere (the A/B build).
+#ifndef PSN_BX_CHAIN_NT
+#define PSN_BX_CHAIN_NT 1
+#endif
+template <int OFF>
+__device__ __forceinline__ void bx_ld_at(bxf4 &v0, bxf4 &v1, bxf4 &v2, bxf4 &v3, unsigned ad) {
+    asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\t"
+                 "ds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %4 offset:%8"
+                 : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
+                 : "v"(ad), "n"(OFF), "n"(OFF + 16), "n"(OFF + 32), "n"(OFF + 48)
+                 : "memory");
+}
+// block B is in flight in its register set (even blocks a, odd blocks c)
+template <int B, int NB>
+__device__ __forceinline__ float chain_nt_from(unsigned ad, float acc, bxf4 &a0, bxf4 &a1, bxf4 &a2, bxf4 &a3, bxf4 &c0,
+                                               bxf4 &c1, bxf4 &c2, bxf4 &c3) {
+    static_assert(64 * NB + 48 < 65536, "the block offsets are 16-bit immediates");
+    if constexpr (B + 1 < NB) {
+        if constexpr (B & 1) {
+            bx_ld_at<64 * (B + 1)>(a0, a1, a2, a3, ad);
+            BX_WAIT4(c0, c1, c2, c3);
+            acc = add16m(acc, c0, c1, c2, c3, true);
+        } else {
+            bx_ld_at<64 * (B + 1)>(c0, c1, c2, c3, ad);
+            BX_WAIT4(a0, a1, a2, a3);
+            acc = add16m(acc, a0, a1, a2, a3, true);
+        }
+        return chain_nt_from<B + 1, NB>(ad, acc, a0, a1, a2, a3, c0, c1, c2, c3);
+    } else if constexpr (B & 1) {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3) : : "memory");
+        return add16m(acc, c0, c1, c2, c3, true);
+    } else {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : : "memory");
+        return add16m(acc, a0, a1, a2, a3, true);
+    }
+}
+__device__ __forceinline__ unsigned bx_lds_addr(const float *p) {
+    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float *)p;
+}
+template <int NB>
+__device__ __forceinline__ float chain_sum_nt(const float *p, float acc PSN_STAMPS_ONLY(, unsigned *first_wait = nullptr)) {
+    const unsigned ad = bx_lds_addr(p);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the counts below are then exact
+    __builtin_amdgcn_s_setprio(3);
+    bxf4 a0, a1, a2, a3, c0, c1, c2, c3;
+#ifdef PSN_LK_STAMPS
+    unsigned long long t0_, t1_;  // the first block's LDS round trip (as chain_sum_pl)
+    PSN_CLK(t0_);
+#endif
+    bx_ld_at<0>(a0, a1, a2, a3, ad);
+#ifdef PSN_LK_STAMPS
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : : "memory");
+    PSN_CLK(t1_);
+    if (first_wait && threadIdx.x == 0) *first_wait += (unsigned)(t1_ - t0_);
+#endif
+    acc = chain_nt_from<0, NB>(ad, acc, a0, a1, a2, a3, c0, c1, c2, c3);
+    __builtin_amdgcn_s_setprio(PSN_BX_PRIO);
+    return acc;
+}
 // XCD-aware workgroup order (MI355X_MICROARCH.md, workgroup dispatch: blocks are
 // dealt round-robin over the 8 XCDs, each with its own L2): hardware block b
 // runs logical workgroup xcd_remap(b), so that logical workgroups [x*q, ...) --

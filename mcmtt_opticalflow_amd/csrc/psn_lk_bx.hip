@@ -53,10 +53,16 @@ struct BxBasePolicy {
     // Off here: the pinned builds keep their code; the two-wave build takes the
     // flag through its own condition (QT in the body)
     static constexpr bool kErrStatusOnly = false;
+    // the chain lanes' tile step (PSN_BX_CHAIN_NT, psn_lk_bx.h): full no-tail tiles
+    // summed by the straight-line chain_sum_nt with the tile geometry taken once
+    // per fallback. Off here: the pinned builds and the two-wave build keep
+    // chain_sum_pl and their loops
+    static constexpr bool kChainNT = false;
 };
 struct BxFwPolicy {
     static constexpr bool kShortWriterGeo = true;
     static constexpr bool kErrStatusOnly = true;
+    static constexpr bool kChainNT = true;
 };
 
 template <int UPT, bool NOTAIL, int NT = kBxNT>

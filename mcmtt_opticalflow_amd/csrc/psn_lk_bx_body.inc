@@ -13,6 +13,16 @@
     constexpr bool QT = NT == kBxNT2;       // quarter-wave fallback tiles
     constexpr int TG = QT ? kBxTile2 : kBxTile;  // threads per fallback tile granule
     constexpr int TPH = 32 / TG;            // tiles per half wave (exactness is decided per half wave)
+    // The chain lanes' tile step of the forward entry (PSN_BX_CHAIN_NT; the two-wave
+    // build measured no gain from it and keeps its loops): a full tile (all TG *
+    // UPT units inside the window, one granule per tile) is NBF whole blocks per
+    // lane chain in regions of stride SF
+    // in planes of pitch PF wherever it lies in the window, so the chain lanes take
+    // their region offset once per fallback and sum the tile by chain_sum_nt<NBF>.
+    // A partial last tile keeps bx_tile_slots_nt and chain_sum_pl.
+    constexpr bool CNT = PSN_BX_CHAIN_NT && NOTAIL && POL::kChainNT;
+    constexpr int NBF = bx_nt_tile_blocks(UPT, TG), SF = bx_nt_tile_S(UPT, TG), PF = bx_nt_tile_P(UPT, TG);
+    static_assert(!CNT || NBF * 16 == TG * UPT, "a full no-tail tile is whole blocks");
     const int tid = threadIdx.x, lane = tid & 63;
     if (A.poison_lds) lds_poison<NT>(smem, A.poison_lds);
     const int g = xcd_remap((int)blockIdx.x, (int)gridDim.x);
@@ -481,6 +491,9 @@
                     writeA(g_first, PL);
                 padA(g_first, PL);
                 __syncthreads();
+                // (CNT) once per fallback: the chain lane's region offset in a full tile
+                [[maybe_unused]] const int roff = cs * PF + cc * SF;
+                [[maybe_unused]] const bool one = HW == 1;  // one granule per tile: a tile inside the window is full
                 for (int g = g_first, t = 0; g <= g_last; g += HW, t ^= 1) {
                     float *cur = PL + t * PCA, *nxt = PL + (t ^ 1) * PCA;
 #ifdef PSN_LK_STAMPS
@@ -497,7 +510,18 @@
                     PSN_CLK_ORDERED(tc1);
                     tc2 = tc3 = tc1;
 #endif
-                    if ((ftid >> 6) == 0) {
+                    bool full = false;  // (CNT) the straight-line step of a full tile
+                    if constexpr (CNT) full = one && TG * UPT * (g + 1) <= U;
+                    if constexpr (CNT) {
+                        if (full && (ftid >> 6) == 0) {
+                            PSN_CLK_ORDERED(tc2);
+                            if (chl && cc < 4) acc = chain_sum_nt<NBF>(cur + roff, acc PSN_STAMPS_ONLY(, &bx_tl[24 - 19]));
+                            PSN_CLK_ORDERED(tc3);
+                            // only the window's last tile can have a pad
+                            if (g + 1 == g_last) padA(g_last, nxt);
+                        }
+                    }
+                    if (!full && (ftid >> 6) == 0) {
                         int sa, ta, nsse, ntail;
                         geoA(g, sa, ta, nsse, ntail);
                         const int S = bx_region(nsse), P = 4 * S + bx_region(ntail);
@@ -723,6 +747,9 @@
                 const int cl = chl ? ftid : 0, cs = cl / 5, cc = cl - 5 * cs;
                 float acc = (float)base0;
                 const int g_last = (U - 1) / (TG * UPT), g_first = h0 * TPH;
+                // (CNT, as the A fallback's) once per fallback: the chain lane's region offset in a full tile
+                [[maybe_unused]] const int roff = cs * PF + cc * SF;
+                [[maybe_unused]] const bool one = HW == 1;
                 // (as the A fallback's geoA_g)
                 auto tile_geo_g = [&](int g, int &sa, int &ta, int &nsse, int &ntail, auto shortT) {
                     const int ua = TG * UPT * g, ub = min(ua + TG * UPT * HW, U);
@@ -972,6 +999,16 @@
                             spin(b, tag(g));
                             PSN_CLK_ORDERED(tf1);
                             float *cur = PL + b * 2 * PC;
+                            bool full = false;  // (CNT) a full tile (split: one granule per tile) has no pad
+                            if constexpr (CNT) full = TG * UPT * (g + 1) <= U;
+                            if constexpr (CNT) {
+                                if (full) {
+                                    PSN_CLK_ORDERED(tf2);
+                                    if (chl && cc < 4) acc = chain_sum_nt<NBF>(cur + roff, acc PSN_STAMPS_ONLY(, &bx_tl[30 - 19]));
+                                    PSN_CLK_ORDERED(tf3);
+                                }
+                            }
+                            if (!full) {
                             int sa, ta, nsse, ntail;
                             tile_geo(g, sa, ta, nsse, ntail);
                             const int S = bx_region(nsse), P = 4 * S + bx_region(ntail);
@@ -985,6 +1022,7 @@
                             if (chl && (!NOTAIL || cc < 4))
                                 acc = chain_sum_pl<NOTAIL>(cur + cs * P + cc * S, len, nbmax, acc PSN_STAMPS_ONLY(, &bx_tl[30 - 19]));
                             PSN_CLK_ORDERED(tf3);
+                            }
                             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                             if (fl == 0) FLG[3 + b] = tag(g);
 #ifdef PSN_LK_STAMPS
@@ -1023,7 +1061,18 @@
                     PSN_CLK_ORDERED(tc0);
                     tc3 = tc4 = tc0;
 #endif
-                    if ((ftid >> 6) == 0) {
+                    bool full = false;  // (CNT) the straight-line step of a full tile
+                    if constexpr (CNT) full = one && TG * UPT * (g + 1) <= U;
+                    if constexpr (CNT) {
+                        if (full && (ftid >> 6) == 0) {
+                            PSN_CLK_ORDERED(tc3);
+                            if (chl && cc < 4) acc = chain_sum_nt<NBF>(cur + roff, acc PSN_STAMPS_ONLY(, &bx_tl[30 - 19]));
+                            PSN_CLK_ORDERED(tc4);
+                            // only the window's last tile can have a pad
+                            if (g + 1 == g_last) pad_tile(g_last, nxt);
+                        }
+                    }
+                    if (!full && (ftid >> 6) == 0) {
                         int sa, ta, nsse, ntail;
                         tile_geo(g, sa, ta, nsse, ntail);
                         const int S = bx_region(nsse), P = 4 * S + bx_region(ntail);

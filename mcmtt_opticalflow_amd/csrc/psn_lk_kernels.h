@@ -332,6 +332,15 @@ __host__ __device__ inline void bx_tile_slots(int ua, int ub, int qw, int nq, in
 __host__ __device__ inline void bx_tile_slots_nt(int ua, int ub, int &sa, int &ta, int &nsse, int &ntail) {
     sa = ua, ta = 0, nsse = ub - ua, ntail = 0;
 }
+// A FULL tile of a no-tail build (all tile * upt units of one granule inside the
+// window) has the same geometry wherever it lies: tile * upt slots per lane
+// chain in whole 16-float blocks, no tail slots. Its block count, region stride S
+// and plane pitch P are constants of the build (bx_region of those counts), so
+// the chain lanes of lk_kernel_fw take them, and their
+// region offset cs * P + cc * S, once per fallback (tests/test_bx_chain_tile_step.py).
+__host__ __device__ constexpr int bx_nt_tile_blocks(int upt, int tile) { return tile * upt / 16; }
+__host__ __device__ constexpr int bx_nt_tile_S(int upt, int tile) { return tile * upt + 4; }
+__host__ __device__ constexpr int bx_nt_tile_P(int upt, int tile) { return 4 * bx_nt_tile_S(upt, tile) + 4; }
 struct BxLayout {
     int jr, un, pb, total;
     __host__ __device__ BxLayout(int w, int h, int upt, int hw = 1, int tile = kBxTile) {

@@ -190,7 +190,7 @@ int plan_query(const PlanCfg &c, const char *filled, const psn_lk_query &q, bool
     const bool forced = c.force_threads != 0;
     if (c.force_large) {
         pq.cls = kClsLg;
-    } else if (pq.single && !c.force_generic) {
+    } else if (pq.single && !c.force_generic && !(c.box_small && pq.bx_upt > 0)) {
         pq.cls = kClsSt;
     } else if (pq.bx_upt > 0 && c.box && !c.force_generic && !forced && !(no_bx16 && pq.bx_upt == 16)) {
         pq.cls = kClsBx;

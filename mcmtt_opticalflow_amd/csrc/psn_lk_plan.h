@@ -50,6 +50,9 @@ struct PlanCfg {
     bool onewave = true;  // ONEWAVE 0: multi-wave iterations in the single-tile kernel
     bool st_ovl = PSN_ST_OVL_DEFAULT != 0;  // ST_OVL 0: every level's A phase in the single-tile prologue
     bool box = true;      // BOX 0: box windows run the row-tiled kernel instead of lk_kernel_bx
+    // BOX 2: lk_kernel_bx also for the windows the single-tile kernel takes (tests:
+    // box windows of one or two fallback tiles)
+    bool box_small = false;
     // BX_WAVES: 0 = planner, 4 = never the two-wave box build, 2 = the two-wave
     // build wherever it fits (psn::bx_two_wave_fits)
     int bx_waves = 0;
