@@ -87,7 +87,10 @@ static int gridfast_impl(psn_lk_ctx *c, int nset, const int *slots, const int *n
         a.out_count = d_cnt + base;
         a.out_total = d_tot ? d_tot + base : nullptr;
         // LDS plan: the widest region a (roi, cell) workgroup can see, the strip
-        // height, the single-pass keypoint list (coordinates packed in 12 bits)
+        // height, the single-pass keypoint list (coordinates packed in 12 bits).
+        // Strip 16 from rw_max 769 on; strip 8 and a shrunken list_cap cannot occur
+        // while kGfMaxRegionW is 1024: strip 16 at rw_max 1024 with the 4096-entry
+        // list is 24 * 1032 + 18 * 1026 (+ 12 to 16 B) + 16 * 1024 + 4 * 4096 = 76,016 B
         int rw_max = 1;
         const int cell_w = (width + p.grid_cols - 1) / p.grid_cols - 6;
         for (int i = 0; i < n; i++) rw_max = std::max(rw_max, std::min(rois[4 * (size_t)(base + i) + 2], cell_w));
