@@ -424,21 +424,10 @@ __device__ __forceinline__ float add16m(float acc, const bxf4 &a, const bxf4 &b,
 // Wave priority of the latency-critical sections of lk_kernel_bx (from the end of
 // a main pass to the start of the next: publish, check, eval, results, solve,
 // iteration head; the A publish / eval) over the throughput sections (A window,
-// main passes) of the other workgroups on the SIMD; the ordered chains run at 3.
-#ifndef PSN_BX_PRIO
-#define PSN_BX_PRIO 1
-#endif
-// b fallback: tiles handed from their writer waves to the chain lanes through
-// LDS flags (three buffers) rather than one workgroup barrier per tile
-#ifndef PSN_BX_FLAGS
-#define PSN_BX_FLAGS 1
-#endif
-// fallback tile geometry of the no-tail builds from the tile's unit range alone
-// (no division by the row's quads; 0: the general formula of the tail builds)
-#ifndef PSN_BX_GEO_NT
-#define PSN_BX_GEO_NT 1
-#endif
-__device__ __forceinline__ void bx_prio_hi() { __builtin_amdgcn_s_setprio(PSN_BX_PRIO); }
+// main passes) of the other workgroups on the SIMD; the ordered chains run at 3
+// and return to kBxPrioHi.
+constexpr int kBxPrioHi = 1;
+__device__ __forceinline__ void bx_prio_hi() { __builtin_amdgcn_s_setprio(kBxPrioHi); }
 __device__ __forceinline__ void bx_prio_lo() { __builtin_amdgcn_s_setprio(0); }
 // UNIFORM (no-tail builds): every chain lane has nbmax blocks, so no block is
 // masked and the adds carry no select on the dependent chain; an odd last
@@ -493,7 +482,7 @@ __device__ __forceinline__ float chain_sum_pl(const float *p, int len, int nbmax
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : : "memory");
-    __builtin_amdgcn_s_setprio(PSN_BX_PRIO);
+    __builtin_amdgcn_s_setprio(kBxPrioHi);
     return acc;
 }
 
@@ -502,10 +491,6 @@ __device__ __forceinline__ float chain_sum_pl(const float *p, int len, int nbmax
 // immediate offset from the one base register, the two register sets
 // and the lgkmcnt(4) discipline of chain_sum_pl<true>, no loop counter, compare,
 // branch or address add between the dependent adds, and no read past the chain.
-// PSN_BX_CHAIN_NT=0 compiles the loops of chain_sum_pl everywhere (the A/B build).
-#ifndef PSN_BX_CHAIN_NT
-#define PSN_BX_CHAIN_NT 1
-#endif
 template <int OFF>
 __device__ __forceinline__ void bx_ld_at(bxf4 &v0, bxf4 &v1, bxf4 &v2, bxf4 &v3, unsigned ad) {
     asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\t"
@@ -558,7 +543,7 @@ __device__ __forceinline__ float chain_sum_nt(const float *p, float acc PSN_STAM
     if (first_wait && threadIdx.x == 0) *first_wait += (unsigned)(t1_ - t0_);
 #endif
     acc = chain_nt_from<0, NB>(ad, acc, a0, a1, a2, a3, c0, c1, c2, c3);
-    __builtin_amdgcn_s_setprio(PSN_BX_PRIO);
+    __builtin_amdgcn_s_setprio(kBxPrioHi);
     return acc;
 }
 // XCD-aware workgroup order (MI355X_MICROARCH.md, workgroup dispatch: blocks are

@@ -53,7 +53,7 @@ struct BxBasePolicy {
     // Off here: the pinned builds keep their code; the two-wave build takes the
     // flag through its own condition (QT in the body)
     static constexpr bool kErrStatusOnly = false;
-    // the chain lanes' tile step (PSN_BX_CHAIN_NT, psn_lk_bx.h): full no-tail tiles
+    // the chain lanes' tile step (chain_sum_nt, psn_lk_bx.h): full no-tail tiles
     // summed by the straight-line chain_sum_nt with the tile geometry taken once
     // per fallback. Off here: the pinned builds and the two-wave build keep
     // chain_sum_pl and their loops

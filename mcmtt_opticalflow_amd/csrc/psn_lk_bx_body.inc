@@ -13,14 +13,14 @@
     constexpr bool QT = NT == kBxNT2;       // quarter-wave fallback tiles
     constexpr int TG = QT ? kBxTile2 : kBxTile;  // threads per fallback tile granule
     constexpr int TPH = 32 / TG;            // tiles per half wave (exactness is decided per half wave)
-    // The chain lanes' tile step of the forward entry (PSN_BX_CHAIN_NT; the two-wave
+    // The chain lanes' tile step of the forward entry (POL::kChainNT; the two-wave
     // build measured no gain from it and keeps its loops): a full tile (all TG *
     // UPT units inside the window, one granule per tile) is NBF whole blocks per
     // lane chain in regions of stride SF
     // in planes of pitch PF wherever it lies in the window, so the chain lanes take
     // their region offset once per fallback and sum the tile by chain_sum_nt<NBF>.
     // A partial last tile keeps bx_tile_slots_nt and chain_sum_pl.
-    constexpr bool CNT = PSN_BX_CHAIN_NT && NOTAIL && POL::kChainNT;
+    constexpr bool CNT = NOTAIL && POL::kChainNT;
     constexpr int NBF = bx_nt_tile_blocks(UPT, TG), SF = bx_nt_tile_S(UPT, TG), PF = bx_nt_tile_P(UPT, TG);
     static_assert(!CNT || NBF * 16 == TG * UPT, "a full no-tail tile is whole blocks");
     const int tid = threadIdx.x, lane = tid & 63;
@@ -42,7 +42,7 @@
     int *X = (int *)smem;                      // chain-check records, two parities
     float *RS = (float *)(X + kBxXInts);       // serial-chain results (wave 0 -> all)
     int *EP = (int *)(RS + 16);                // err partial sums per wave
-    // b-fallback tile hand-off flags (PSN_BX_FLAGS): ready[3], consumed[3], and
+    // b-fallback tile hand-off flags (the split path below): ready[3], consumed[3], and
     // FLG[6] = a hand-off wait ran out of its bound (never expected: the point is
     // then reported failed, see the result writes)
     volatile int *FLG = (volatile int *)(RS + 24);
@@ -298,7 +298,7 @@
                 float acc = (float)base0;  // |base0| <= 2^24: exact
                 const int g_last = (U - 1) / (TG * UPT), g_first = h0 * TPH;
                 // The tile's chain slots (bx_tile_slots). No-tail builds take the short form
-                // (PSN_BX_GEO_NT: no division on the tile loop's path) everywhere but in the
+                // (bx_tile_slots_nt: no division on the tile loop's path) everywhere but in the
                 // half-wave writers, writeA_nt and the b fallback's write_tile_nt (shortT
                 // false): those hold the register peak of the <4 / 8 / 10, true> builds,
                 // which moves with the form (121 / 151 / 164 for 122 / 152 / 167, the
@@ -306,7 +306,7 @@
                 // entry (POL::kShortWriterGeo) takes the short form there as well.
                 auto geoA_g = [&](int g, int &sa, int &ta, int &nsse, int &ntail, auto shortT) {
                     const int ua = TG * UPT * g, ub = min(ua + TG * UPT * HW, U);
-                    if constexpr (NOTAIL && PSN_BX_GEO_NT && (decltype(shortT)::value || POL::kShortWriterGeo)) {
+                    if constexpr (NOTAIL && (decltype(shortT)::value || POL::kShortWriterGeo)) {
                         static_assert((TG * UPT) % 16 == 0, "a full no-tail tile has no pad");
                         bx_tile_slots_nt(ua, ub, sa, ta, nsse, ntail);
                     } else {
@@ -753,7 +753,7 @@
                 // (as the A fallback's geoA_g)
                 auto tile_geo_g = [&](int g, int &sa, int &ta, int &nsse, int &ntail, auto shortT) {
                     const int ua = TG * UPT * g, ub = min(ua + TG * UPT * HW, U);
-                    if constexpr (NOTAIL && PSN_BX_GEO_NT && (decltype(shortT)::value || POL::kShortWriterGeo)) {
+                    if constexpr (NOTAIL && (decltype(shortT)::value || POL::kShortWriterGeo)) {
                         static_assert((TG * UPT) % 16 == 0, "a full no-tail tile has no pad");
                         bx_tile_slots_nt(ua, ub, sa, ta, nsse, ntail);
                     } else {
@@ -955,7 +955,6 @@
                     float *rg = buf + cs * P + cc * S;
                     for (int i = len; i < ((len + 15) & ~15); i++) rg[i] = 0.f;
                 };
-#if PSN_BX_FLAGS
                 if (split) {
                     // Three tile buffers, handed over through LDS flags instead of a
                     // workgroup barrier per tile: wave w writes its tiles 2w, 2w+1 as
@@ -1038,9 +1037,7 @@
 #endif
                         }
                     }
-                } else
-#endif
-                {
+                } else {
                 if constexpr (QT)
                     write_tile_qt(g_first, PL, 0);
                 else

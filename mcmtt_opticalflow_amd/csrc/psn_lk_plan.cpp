@@ -31,13 +31,9 @@ namespace {
 // The planner's default for the windows the two-wave box build fits
 // (PSN_LK_VARIANT_BX_WAVES 0); DESIGN.md section 8 has the measurement behind it.
 constexpr bool kBxPlanTwoWave = true;
-// ... and for the launches the forward entry fits (PSN_LK_VARIANT_FW 0): the
+// The launches the forward entry fits take it by default (PSN_LK_VARIANT_FW 0): the
 // entry's gains are measured against lk_kernel_bx<10, true> in DESIGN.md section 8.
-// (PSN_BX_PLAN_FW=0: a build whose planner never takes it, for A/B runs of the benchmark)
-#ifndef PSN_BX_PLAN_FW
-#define PSN_BX_PLAN_FW 1
-#endif
-constexpr bool kBxPlanFw = PSN_BX_PLAN_FW != 0;
+// The runtime variant fw=1 plans as if it did not exist.
 
 // One query as planned: its device descriptor and the kernels that can take it.
 struct PlannedQuery {
@@ -350,7 +346,7 @@ void plan_launch(const PlanCfg &c, PlannedQuery *const *grp, int n, int cls, int
         L.nt = nt;
         // the forward entry of the build: a launch-time choice (same queries, same
         // LDS plan, same launch group and key)
-        L.fw = bx_fw_fits(upt, notail, nt) && (c.fw == 2 || (c.fw == 0 && kBxPlanFw));
+        L.fw = bx_fw_fits(upt, notail, nt) && c.fw != 1;
         L.lds = lds_bx;
         return;
     }

@@ -11,15 +11,6 @@
 #include "psn_lk.h"
 #include "psn_lk_kernels.h"
 
-#ifndef PSN_ST_OVL_DEFAULT
-#define PSN_ST_OVL_DEFAULT 1
-#endif
-// the default of the ERR_STATUS variant (0: a build that ignores the flag, for A/B
-// runs of the benchmark, which sets no variants)
-#ifndef PSN_LK_PLAN_ERR_STATUS
-#define PSN_LK_PLAN_ERR_STATUS 1
-#endif
-
 namespace psn {
 
 // The last-error text of a context (psn_lk_last_error); returns `code`.
@@ -48,7 +39,7 @@ struct PlanCfg {
     int force_threads = 0;
     bool force_generic = false;
     bool onewave = true;  // ONEWAVE 0: multi-wave iterations in the single-tile kernel
-    bool st_ovl = PSN_ST_OVL_DEFAULT != 0;  // ST_OVL 0: every level's A phase in the single-tile prologue
+    bool st_ovl = true;   // ST_OVL 0 (the benchmark's st_ovl=0): every level's A phase in the single-tile prologue
     bool box = true;      // BOX 0: box windows run the row-tiled kernel instead of lk_kernel_bx
     // BOX 2: lk_kernel_bx also for the windows the single-tile kernel takes (tests:
     // box windows of one or two fallback tiles)
@@ -56,12 +47,12 @@ struct PlanCfg {
     // BX_WAVES: 0 = planner, 4 = never the two-wave box build, 2 = the two-wave
     // build wherever it fits (psn::bx_two_wave_fits)
     int bx_waves = 0;
-    // FW: 0 = planner, 1 = never the forward entry (lk_kernel_fw), 2 = the forward
+    // FW: 0 = planner, 1 = never the forward entry (lk_kernel_fw; the benchmark's fw=1), 2 = the forward
     // entry wherever it fits (psn::bx_fw_fits)
     int fw = 0;
     // ERR_STATUS: 1 = PSN_LK_ERR_STATUS_ONLY is dropped from every query's flags
-    // (the launches write err as without it)
-    bool err_status_ignore = PSN_LK_PLAN_ERR_STATUS == 0;
+    // (the launches write err as without it; the benchmark's err_status=1)
+    bool err_status_ignore = false;
     // TILED_LDS: LDS budget of a tiled-kernel workgroup (bytes); 76 KB keeps two
     // workgroups per CU (Tracker2D box windows: 64x64 backward, 64x160 forward at 1080p)
     int tiled_lds = 76 * 1024;

@@ -69,8 +69,8 @@ def test_binade_model_edges():
 
 
 def _runs(L, terms, seg_len, fs):
-    """oracle_chain_runs (the per-thread parity records with local HARD runs of
-    psn_lk_xb.h) from segment fs, whose exact start every earlier prefix must
+    """oracle_chain_runs (the per-thread parity records with local HARD runs,
+    DESIGN.md §8) from segment fs, whose exact start every earlier prefix must
     allow: None when the chain is not exact before fs or the model aborts."""
     L.oracle_chain_runs.argtypes = [_f32p, _i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p]
     L.oracle_chain_runs.restype = ctypes.c_float
@@ -92,7 +92,7 @@ def _runs(L, terms, seg_len, fs):
 
 @pytest.mark.parametrize("seg_len", [1, 7, 25, 64])
 def test_parity_record_model_matches_sequential(seg_len):
-    """The b fallback by parity records (psn_lk_xb.h, build parameter PSN_LG_XB):
+    """The b fallback by parity records (measured and retired):
     bit for bit the sequential float sum, on biased and unbiased chains of
     LK-sized integer products, started at several segments."""
     L = _lib()

@@ -6,7 +6,7 @@ the stamps build, mcmtt_opticalflow_amd/lib/libpsn_lk_stamps.so). Tracker2D-like
 Prints per-workgroup mean / slowest cycles per phase (s_memtime ticks, thread
 0's view), the serial-chain fraction of the iterations and, per fallback tile,
 the chain lane's time split four ways for the A and the b fallback.
-STAMPS_LIB=path runs another stamps build (make ... EXTRA=-DPSN_BX_GEO_NT=0).
+STAMPS_LIB=path runs another stamps build.
 
   WIN=64 WINH=160 NPTS=630 python tools/bx_stamps.py
   WIN=64 WINH=160 NPTS=2048 VARIANTS=fw=1 python tools/bx_stamps.py        # lk_kernel_bx<10, true>, not its forward entry lk_kernel_fw
