@@ -294,6 +294,10 @@ int psn_lk_timing_launches(psn_lk_ctx *ctx, int cap, double *ms, int *tag, int *
  * and results as lk_kernel_bx<UPT, no-tail>, whose tag the call keeps above:
  * the tag names the build, the entry what was launched). */
 int psn_lk_timing_entries(psn_lk_ctx *ctx, int cap, int *entry, int *n);
+/* The same calls' workgroups (one per point) planned on the sliding A pass of
+ * the two-wave box build, lk_kernel_bx<8, no-tail, 128>: its windows whose rows
+ * are a multiple of 8 quads (w % 32 == 0); 0 where the call launched none. */
+int psn_lk_timing_slides(psn_lk_ctx *ctx, int cap, int *wgs, int *n);
 
 /* Kernel-variant selection for tests and experiments (never read from the
  * environment: a product context always runs the planner's choice). Applies

@@ -176,6 +176,17 @@ def timing_entries(L, ctx, cap: int):
     return [entry[i] for i in range(n.value)]
 
 
+def timing_slides(L, ctx, cap: int):
+    """psn_lk_timing_slides -> per timed LK call, its workgroups planned on the
+    sliding A pass of the two-wave box build."""
+    wgs = (ctypes.c_int * max(cap, 1))()
+    n = ctypes.c_int()
+    rc = L.psn_lk_timing_slides(ctx, cap, wgs, ctypes.byref(n))
+    if rc != 0:
+        raise PsnLkError(rc, "psn_lk_timing_slides")
+    return [wgs[i] for i in range(n.value)]
+
+
 def launched_kernels(L, ctx, cap: int):
     """Names of the kernels the timed LK calls launched, by entry
     (lk_kernel_fw<10, true> where the forward entry ran the 10-unit no-tail build)."""
@@ -298,6 +309,8 @@ def load(path: str | None = None):
     L.psn_lk_timing_launches.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ip),
                                          ctypes.POINTER(ip)]
     L.psn_lk_timing_entries.argtypes = [vp, ip, ctypes.POINTER(ip), ctypes.POINTER(ip)]
+    if hasattr(L, "psn_lk_timing_slides"):  # (absent from the A/B experiments' older builds only)
+        L.psn_lk_timing_slides.argtypes = [vp, ip, ctypes.POINTER(ip), ctypes.POINTER(ip)]
     L.psn_lk_debug_set_stamps.argtypes = [vp, vp]
     L.psn_lk_debug_count_samples.argtypes = [vp, ip]
     L.psn_lk_debug_read_samples.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]

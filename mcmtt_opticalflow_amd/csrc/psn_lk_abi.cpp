@@ -461,6 +461,7 @@ int psn_lk_enable_timing(psn_lk_ctx *c, int capacity, int every) {
     c->tcap = capacity;
     c->track_tag.assign((size_t)capacity, 0);
     c->track_entry.assign((size_t)capacity, 0);
+    c->track_slide.assign((size_t)capacity, 0);
     c->every = every;
     return PSN_LK_OK;
 }
@@ -512,6 +513,14 @@ int psn_lk_timing_entries(psn_lk_ctx *c, int cap, int *entry, int *n) {
     if (!c || cap < 0 || !n || (cap > 0 && !entry)) return PSN_LK_ERR_ARG;
     const long k = std::min<long>(std::min<long>(c->t_track.n, c->tcap), cap);
     for (long i = 0; i < k; i++) entry[i] = c->track_entry[(size_t)i];
+    *n = (int)k;
+    return PSN_LK_OK;
+}
+
+int psn_lk_timing_slides(psn_lk_ctx *c, int cap, int *wgs, int *n) {
+    if (!c || cap < 0 || !n || (cap > 0 && !wgs)) return PSN_LK_ERR_ARG;
+    const long k = std::min<long>(std::min<long>(c->t_track.n, c->tcap), cap);
+    for (long i = 0; i < k; i++) wgs[i] = c->track_slide[(size_t)i];
     *n = (int)k;
     return PSN_LK_OK;
 }
@@ -902,6 +911,7 @@ static int track_device_impl(psn_lk_ctx *c, const psn_lk_query *q, int nq, const
     if (ti >= 0 && plan.tag) {
         c->track_tag[(size_t)ti] = plan.tag;
         c->track_entry[(size_t)ti] = plan.entry;
+        c->track_slide[(size_t)ti] = plan.slide_wgs;
     }
     if ((rc = flush_pending(c))) return rc;  // no launch took it (no single-tile launch)
     if ((rc = psn::timer_end(c, c->t_track, c->stream, ti))) return rc;

@@ -382,6 +382,134 @@ __device__ __forceinline__ void bx_unit(const uint32_t *P32, int PM, int sh, int
     YPk[1] = pack_w(iy[2], iy[3]);
 }
 
+// The sliding A pass (the two-wave build of lk_kernel_bx where a thread's run of
+// units stays inside one window row, bx_slides): unit q + 1's byte window starts
+// at byte 4 of unit q's, so its dwords d0, d1, its even pairs E[r][0..1], its
+// column sums SV / DV[0..1] and its derivative pair DXp / DYp[o][0] are unit q's
+// d1, d2, E[r][2..3], SV / DV[2..3] and DXp / DYp[o][2] -- the same absolute
+// columns and rows, hence the same border masks. What a unit hands to its right
+// neighbour (pair values as their bits: the caller pins them as registers):
+struct BxCarry {
+    uint32_t d2[4];             // the rows' last patch dword
+    unsigned E[2][2];           // E[1..2][2..3]: the bilinear I values read them
+    unsigned SV[2][2], DV[2][2];  // SV / DV[2..3] of the derivative rows o = 0, 1
+    unsigned DX[2], DY[2];      // the masked DXp / DYp[o][2]
+};
+// bx_unit<IN, true> of the unit at p (its first patch dword of window row yy; quad
+// column qq, for the masks) with the same results bit for bit for every unit
+// inside the window. FIRST: the run's
+// first unit, computed in full; else one new dword per row and the new columns
+// only, the rest from C. Both leave C for the next unit. The odd pairs come from
+// the even ones (alignbyte by 2 bytes), so the rows' low bytes are not kept.
+// Wa, Wb: the packed bilinear weights (iw00, iw01), (iw10, iw11) -- both ZERO for
+// a run past the window: its gradients are then (0 + 8192) >> 14 = 0 with no mask
+// per pixel, and its I values, which nothing reads, are 0 as well.
+template <bool IN, bool FIRST>
+__device__ __forceinline__ void bx_unit_slide(const uint32_t *p, int PM, int sh, int yy, int qq, int ipx, int ipy,
+                                              int cols, int rows, unsigned Wa, unsigned Wb, int c256, int c8192,
+                                              BxCarry &C, unsigned (&IPk)[2], unsigned (&XPk)[2], unsigned (&YPk)[2],
+                                              int &gmx, int &gmn) {
+    unsigned E[4][4];  // (not FIRST: rows 0 and 3 hold their pairs 2, 3 only)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const uint32_t *pr = p + r * PM;
+        const uint32_t d2 = pr[2];
+        uint32_t hi;
+        if constexpr (FIRST) {
+            const uint32_t d0 = pr[0], d1 = pr[1];
+            const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, sh);
+            hi = __builtin_amdgcn_alignbyte(d2, d1, sh);
+            E[r][0] = __builtin_amdgcn_perm(hi, lo, 0x0c010c00u);
+            E[r][1] = __builtin_amdgcn_perm(hi, lo, 0x0c030c02u);
+        } else {
+            hi = __builtin_amdgcn_alignbyte(d2, C.d2[r], sh);
+            if (r == 1 || r == 2) {
+                E[r][0] = C.E[r - 1][0];
+                E[r][1] = C.E[r - 1][1];
+            }
+        }
+        E[r][2] = __builtin_amdgcn_perm(hi, hi, 0x0c010c00u);
+        E[r][3] = __builtin_amdgcn_perm(hi, hi, 0x0c030c02u);
+        C.d2[r] = d2;
+        if (r == 1 || r == 2) {
+            C.E[r - 1][0] = E[r][2];
+            C.E[r - 1][1] = E[r][3];
+        }
+    }
+    unsigned cm[3];
+#pragma unroll
+    for (int kk = 0; kk < 3; kk++)
+        cm[kk] = IN ? ~0u
+                    : ((unsigned)(ipx + 4 * qq + 2 * kk) < (unsigned)cols ? 0xffffu : 0u) |
+                          ((unsigned)(ipx + 4 * qq + 2 * kk + 1) < (unsigned)cols ? 0xffff0000u : 0u);
+    unsigned DXp[2][3], DYp[2][3];
+    const s16x2 k3 = {3, 3}, k10 = {10, 10};
+    auto pr2 = [](unsigned v) { return __builtin_bit_cast(s16x2, v); };
+#pragma unroll
+    for (int o = 0; o < 2; o++) {
+        const unsigned rm = IN || (unsigned)(ipy + yy + o) < (unsigned)rows ? ~0u : 0u;
+        s16x2 SV[4], DV[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) {
+            if (!FIRST && kk < 2) {
+                SV[kk] = pr2(C.SV[o][kk]);
+                DV[kk] = pr2(C.DV[o][kk]);
+            } else {
+                SV[kk] = (pr2(E[o][kk]) + pr2(E[o + 2][kk])) * k3 + pr2(E[o + 1][kk]) * k10;
+                DV[kk] = pr2(E[o + 2][kk]) - pr2(E[o][kk]);
+            }
+        }
+#pragma unroll
+        for (int kk = 0; kk < 3; kk++) {
+            if (!FIRST && kk == 0) {
+                DXp[o][0] = C.DX[o];
+                DYp[o][0] = C.DY[o];
+                continue;
+            }
+            const s16x2 dvo = pr2(__builtin_amdgcn_alignbyte(__builtin_bit_cast(unsigned, DV[kk + 1]),
+                                                             __builtin_bit_cast(unsigned, DV[kk]), 2));
+            const s16x2 dx = SV[kk + 1] - SV[kk];
+            const s16x2 dy = (DV[kk] + DV[kk + 1]) * k3 + dvo * k10;
+            DXp[o][kk] = __builtin_bit_cast(unsigned, dx) & cm[kk] & rm;
+            DYp[o][kk] = __builtin_bit_cast(unsigned, dy) & cm[kk] & rm;
+        }
+#pragma unroll
+        for (int kk = 0; kk < 2; kk++) {
+            C.SV[o][kk] = __builtin_bit_cast(unsigned, SV[2 + kk]);
+            C.DV[o][kk] = __builtin_bit_cast(unsigned, DV[2 + kk]);
+        }
+        C.DX[o] = DXp[o][2];
+        C.DY[o] = DYp[o][2];
+    }
+    // pairs (i, i + 1) of rows 1, 2: the odd ones shifted out of the even ones
+    const unsigned b1p[4] = {__builtin_amdgcn_alignbyte(E[1][1], E[1][0], 2), E[1][1],
+                             __builtin_amdgcn_alignbyte(E[1][2], E[1][1], 2), E[1][2]};
+    const unsigned b2p[4] = {__builtin_amdgcn_alignbyte(E[2][1], E[2][0], 2), E[2][1],
+                             __builtin_amdgcn_alignbyte(E[2][2], E[2][1], 2), E[2][2]};
+    int ix[4], iy[4], iv[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int h = i >> 1;
+        const unsigned x0 = (i & 1) ? __builtin_amdgcn_alignbyte(DXp[0][h + 1], DXp[0][h], 2) : DXp[0][h];
+        const unsigned x1 = (i & 1) ? __builtin_amdgcn_alignbyte(DXp[1][h + 1], DXp[1][h], 2) : DXp[1][h];
+        const unsigned y0_ = (i & 1) ? __builtin_amdgcn_alignbyte(DYp[0][h + 1], DYp[0][h], 2) : DYp[0][h];
+        const unsigned y1_ = (i & 1) ? __builtin_amdgcn_alignbyte(DYp[1][h + 1], DYp[1][h], 2) : DYp[1][h];
+        iv[i] = sdot2(b2p[i], Wb, sdot2k(b1p[i], Wa, c256)) >> 9;
+        const int gx = sdot2(x1, Wb, sdot2k(x0, Wa, c8192)) >> 14;
+        const int gy = sdot2(y1_, Wb, sdot2k(y0_, Wa, c8192)) >> 14;
+        ix[i] = gx;
+        iy[i] = gy;
+        gmx = max(gmx, max(ix[i], iy[i]));
+        gmn = min(gmn, min(ix[i], iy[i]));
+    }
+    IPk[0] = pack_w(iv[0], iv[1]);
+    IPk[1] = pack_w(iv[2], iv[3]);
+    XPk[0] = pack_w(ix[0], ix[1]);
+    XPk[1] = pack_w(ix[2], ix[3]);
+    YPk[0] = pack_w(iy[0], iy[1]);
+    YPk[1] = pack_w(iy[2], iy[3]);
+}
+
 // Quarter-wave tiles (the two-wave build of lk_kernel_bx): one output of the 4 x 4
 // transpose of registers r0..r3 over the wave's four 16-lane rows -- lane (row r,
 // i) gets r_r of lane (row TQ, i). v_permlane32_swap exchanges the upper half of

@@ -167,6 +167,8 @@
         // the I patch bytes; the 15 A chains (sum x class) as runs ----
         float sA[3];  // the raw A11, A12, A22 sums
         nwin++;
+        // the two-wave build alone has the sliding A pass (uniform per query: a scalar branch)
+        const bool slide = QT && bx_slides(w, NT);
         {
             const int sh = (ipx - 1) & 3;
             int T11[5] = {0, 0, 0, 0, 0}, T22[5] = {0, 0, 0, 0, 0}, T12[5] = {0, 0, 0, 0, 0};
@@ -176,10 +178,44 @@
             // 4 QW + 1, rows ipy .. ipy + h): no border masks (uniform)
             const bool interior = ipx >= 0 && ipy >= 0 && ipx + 4 * QW + 2 <= cols && ipy + h + 1 <= rows;
             const int c256 = 1 << 8, c8192 = 1 << 13;  // scalar accumulators of the VOP3 v_dot2
-            auto apass = [&](auto inner) {
+            auto apass = [&](auto inner, auto slideT) {
             constexpr bool IN = decltype(inner)::value;
             int y = y0, q = q0;
             asm volatile("" : "+v"(y), "+v"(q));  // opaque: no per-unit address hoisting (VGPRs)
+            if constexpr (decltype(slideT)::value) {
+                // the sliding pass (bx_slides: the run is UPT adjacent quads of one window
+                // row, all inside the window or all past it): the first unit in full, each
+                // later one from its left neighbour's carry and one new dword per row.
+                // A run past the window reads the quads of row 0 with zero weights: zero
+                // gradients (and I values nothing reads: the thread's gmax is 0, and the
+                // fallback writers and the err pass skip units past U)
+                const bool uv = u0 < U;
+                const int yy = uv ? y : 0, qq = uv ? q : 0;
+                const uint32_t *p0 = P32 + yy * PM + qq;
+                const unsigned Wa = uv ? pack_w(iw00, iw01) : 0u, Wb = uv ? pack_w(iw10, iw11) : 0u;
+                BxCarry C;
+#pragma unroll
+                for (int k = 0; k < UPT; k++) {
+                    if (k == 0)
+                        bx_unit_slide<IN, true>(p0, PM, sh, yy, qq, ipx, ipy, cols, rows, Wa, Wb, c256, c8192, C, IP[k],
+                                                XP[k], YP[k], gmx, gmn);
+                    else
+                        bx_unit_slide<IN, false>(p0 + k, PM, sh, yy, qq + k, ipx, ipy, cols, rows, Wa, Wb, c256, c8192, C,
+                                                 IP[k], XP[k], YP[k], gmx, gmn);
+                    // materialize the unit's results and its carry here (as below)
+                    asm volatile("" : "+v"(IP[k][0]), "+v"(IP[k][1]), "+v"(XP[k][0]), "+v"(XP[k][1]), "+v"(YP[k][0]),
+                                 "+v"(YP[k][1]), "+v"(gmx), "+v"(gmn));
+                    if (k + 1 < UPT) {
+                        asm volatile("" : "+v"(C.d2[0]), "+v"(C.d2[1]), "+v"(C.d2[2]), "+v"(C.d2[3]), "+v"(C.E[0][0]),
+                                     "+v"(C.E[0][1]), "+v"(C.E[1][0]), "+v"(C.E[1][1]), "+v"(C.DX[0]), "+v"(C.DX[1]),
+                                     "+v"(C.DY[0]), "+v"(C.DY[1]));
+                        asm volatile("" : "+v"(C.SV[0][0]), "+v"(C.SV[0][1]), "+v"(C.SV[1][0]), "+v"(C.SV[1][1]),
+                                     "+v"(C.DV[0][0]), "+v"(C.DV[0][1]), "+v"(C.DV[1][0]), "+v"(C.DV[1][1]));
+                    }
+                    __builtin_amdgcn_sched_barrier(0);  // one unit at a time (register pressure)
+                }
+                return;
+            }
 #pragma unroll
             for (int k = 0; k < UPT; k++) {
                 const bool uv = u0 + k < U;
@@ -197,10 +233,16 @@
                 __builtin_amdgcn_sched_barrier(0);  // one unit at a time (register pressure)
             }
             };
-            if (interior)
-                apass(std::true_type());
-            else
-                apass(std::false_type());
+            if constexpr (QT) {
+                if (slide && interior)
+                    apass(std::true_type(), std::true_type());
+                else if (slide)
+                    apass(std::false_type(), std::true_type());
+            }
+            if (!slide && interior)
+                apass(std::true_type(), std::false_type());
+            else if (!slide)
+                apass(std::false_type(), std::false_type());
             gmax = max(gmx, -gmn);
             // A products of the window values, units in pairs (a second pass keeps
             // the Scharr temporaries and the chain runs apart): v_mad_i32_i16 on the

@@ -135,6 +135,7 @@ struct psn_lk_ctx {
     CallTimer t_push, t_track;
     std::vector<int> track_tag;  // per timed track call: the kernel it ran (psn_lk_timing_launches)
     std::vector<int> track_entry;  // ... and the entry of that kernel (psn_lk_timing_entries)
+    std::vector<int> track_slide;  // ... and its workgroups on the sliding A pass (psn_lk_timing_slides)
     int every = 1;               // time every `every`-th call of each kind
     std::string err;
 };

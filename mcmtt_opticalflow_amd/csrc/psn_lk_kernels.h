@@ -359,6 +359,11 @@ __host__ __device__ inline bool bx_two_wave_fits(int w, int h, bool notail) {
     return notail && (long)h * bx_qw(w) <= kBxNT2 * kBxUPT2 &&
            BxLayout(w, h, kBxUPT2, 1, kBxTile2).total <= kBxLdsTarget6;
 }
+// The two-wave build's A pass slides along a thread's run of units (bx_unit_slide,
+// psn_lk_bx.h) where no run wraps a window row: thread t's run starts at unit
+// t * kBxUPT2, so iff the row's quads are a multiple of kBxUPT2. A run is then
+// also wholly inside or wholly past the window's h * qw units. Uniform per query.
+__host__ __device__ inline bool bx_slides(int w, int nt) { return nt == kBxNT2 && bx_qw(w) % kBxUPT2 == 0; }
 // Row tiles of the (rare) err chain fallback: one row-major plane.
 inline int bx_err_rows(int w, int h, int pb) {
     for (int t = h; t >= 1; t--)

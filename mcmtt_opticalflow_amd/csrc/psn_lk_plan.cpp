@@ -340,6 +340,7 @@ void plan_launch(const PlanCfg &c, PlannedQuery *const *grp, int n, int cls, int
                    BxLayout(d.win_w, d.win_h, upt, d.bx_hw + 1, tile).total <= bx_lds_target(upt, notail, nt))
                 d.bx_hw++;
             lds_bx = std::max(lds_bx, BxLayout(d.win_w, d.win_h, upt, d.bx_hw, tile).total);
+            if (bx_slides(d.win_w, nt)) L.slide_wgs += d.num_pts;
         }
         L.upt = upt;
         L.notail = notail;
@@ -383,6 +384,7 @@ int plan_call(const PlanCfg &cfg, const psn_lk_query *q, int nq, const char *fil
     out.used_slots.clear();
     out.tag = 0;
     out.entry = 0;
+    out.slide_wgs = 0;
     // plan every query first: a bad one fails the call before anything is launched
     std::vector<PlannedQuery> plan;
     plan.reserve((size_t)nq);
@@ -448,6 +450,7 @@ int plan_call(const PlanCfg &cfg, const psn_lk_query *q, int nq, const char *fil
         }
         if (n) flush(g);
     }
+    for (const LkLaunchPlan &L : out.launches) out.slide_wgs += L.slide_wgs;
     if (!groups.empty()) {
         const size_t dom = (size_t)(std::max_element(group_px.begin(), group_px.end()) - group_px.begin());
         out.tag = kernel_tag(groups[dom].first, groups[dom].second) + (groups.size() > 1 ? 1000 : 0);

@@ -90,6 +90,7 @@ struct LkLaunchPlan {
     int upt = 0;                   // lk_kernel_bx: units per thread
     bool notail = false;           // + its no-tail build
     bool fw = false;               // + its forward entry, lk_kernel_fw<upt, notail, nt>
+    int slide_wgs = 0;             // + its workgroups whose A pass slides (psn::bx_slides)
     // lk_kernel_lg<key>: int2s of one HBM window slot; the grid strides over the points
     long long lg_slot = 0;
     int grid = 0;
@@ -107,6 +108,8 @@ struct LkCallPlan {
     int tag = 0;
     // the same with entry_tag: which entry of that kernel runs
     int entry = 0;
+    // workgroups of the call whose A pass slides (psn::bx_slides; psn_lk_timing_slides)
+    int slide_wgs = 0;
 };
 
 // HBM budget of one stream's large-window slots: one slot per point up to it,
