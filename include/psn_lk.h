@@ -165,6 +165,42 @@ int psn_lk_create_scaled(int device, int width, int height, double scale, int ri
 int psn_lk_source_size(psn_lk_ctx *ctx, int *w, int *h);
 int psn_lk_scale(psn_lk_ctx *ctx, double *s);
 
+/* ---- frame classes: one context for cameras of different frame sizes ----
+ * The reference sizes each CPSNWhere_Tracker2D from its own camera
+ * (PSNWhere_Tracker2D.cpp:118-119; the ring from each frame's cols and rows,
+ * :258-262). A context of several frame classes holds, per class, ring_slots
+ * pyramids for source frames of width x height; one scale for all of them, class
+ * k's LK size being psn_lk_scaled_size of its own source size (a class whose LK
+ * size equals its source size resizes nothing). User slots are numbered
+ * consecutively, class after class (psn_lk_class_slots); the two scratch slots of
+ * psn_calc_optical_flow_pyr_lk come last and belong to class 0, so that call,
+ * psn_lk_level_size and psn_lk_source_size speak of class 0. Every call that
+ * takes a slot uses the slot's class: a push checks the frame (a JPEG: the
+ * file's size) against the class's source size, psn_lk_read_level returns the
+ * class's level sizes, GridFAST clamps rois to the class's LK size (sets of
+ * several classes run as launches per class, results as if each set ran
+ * alone), psn_lk_box_histograms clips rects to the class's source size. A
+ * query whose prev_slot and next_slot lie in different classes is
+ * PSN_LK_ERR_ARG (psn_lk_last_error names both slots) and fails the call
+ * before anything is launched; the queries of one track call otherwise mix
+ * classes freely, one launch per (kernel, frame class). psn_lk_create and
+ * psn_lk_create_scaled are the one-class cases.
+ * PSN_LK_ERR_ARG: ncls outside [1, PSN_LK_MAX_FRAME_CLASSES], a size or
+ * ring_slots <= 0, a bad scale, an LK size below 1 px. An added group of entry
+ * points: PSN_LK_ABI_VERSION stays. */
+#define PSN_LK_MAX_FRAME_CLASSES 8
+typedef struct psn_lk_frame_class {
+    int width, height; /* source size */
+    int ring_slots;
+} psn_lk_frame_class;
+int psn_lk_create_classes(int device, const psn_lk_frame_class *cls, int ncls, double scale, int max_level_cap,
+                          psn_lk_ctx **out);
+int psn_lk_num_classes(psn_lk_ctx *ctx);                      /* < 0 on a null context */
+int psn_lk_slot_class(psn_lk_ctx *ctx, int slot, int *cls);   /* user and scratch slots */
+int psn_lk_class_slots(psn_lk_ctx *ctx, int cls, int *first_slot, int *nslots); /* its user slots */
+int psn_lk_class_source_size(psn_lk_ctx *ctx, int cls, int *w, int *h);
+int psn_lk_class_level_size(psn_lk_ctx *ctx, int cls, int level, int *w, int *h);
+
 /* Use an external HIP stream (hipStream_t as void*); NULL restores the
  * context's own stream. */
 int psn_lk_set_stream(psn_lk_ctx *ctx, void *hip_stream);

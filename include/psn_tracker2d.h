@@ -283,6 +283,25 @@ typedef struct psn_t2d_group psn_t2d_group;
 int psn_t2d_group_create(int device, int ncams, const unsigned *cam_ids, int width, int height, psn_t2d_group **out);
 int psn_t2d_group_create_scaled(int device, int ncams, const unsigned *cam_ids, int width, int height, double scale,
                                 psn_t2d_group **out);
+/* Cameras with their own frame sizes: widths[c] x heights[c] is camera c's
+ * (source) size, as the reference sizes every CPSNWhere_Tracker2D from its own
+ * camera's calibration (PSNWhere_Tracker2D.cpp:118-119) -- the PETS.S2.L1 preset
+ * {1, 5, 7} mixes 768x576 and 720x576 views. One scale for all. Cameras of equal
+ * size share a frame class of the group's LK context (psn_lk_create_classes,
+ * include/psn_lk.h), classes numbered in order of first appearance; more than
+ * PSN_LK_MAX_FRAME_CLASSES distinct sizes is PSN_LK_ERR_ARG. Per camera: the size
+ * of pushed frames (a JPEG of another size, or a stride below the camera's row,
+ * is PSN_LK_ERR_ARG), the LK size, the GridFAST roi's crop, the level truncation
+ * of the backward and forward windows, and the appearance crop
+ * (psn_t2d_appearance_rect with the camera's own size). Everything else of the
+ * group keeps its contract; the cameras' LK work still shares the group's calls,
+ * one launch per (kernel, frame class). psn_t2d_group_create and
+ * psn_t2d_group_create_scaled are the all-equal case. An added pair of entry
+ * points: PSN_T2D_ABI_VERSION stays. */
+int psn_t2d_group_create_sizes(int device, int ncams, const unsigned *cam_ids, const int *widths, const int *heights,
+                               double scale, psn_t2d_group **out);
+/* camera `cam`'s frame size and the size its flow path runs at (each pointer nullable) */
+int psn_t2d_group_camera_size(psn_t2d_group *g, int cam, int *width, int *height, int *lk_width, int *lk_height);
 void psn_t2d_group_destroy(psn_t2d_group *g);
 const char *psn_t2d_group_last_error(psn_t2d_group *g);
 void *psn_t2d_group_lk_context(psn_t2d_group *g);

@@ -74,6 +74,13 @@ class LkQuery(ctypes.Structure):
     ]
 
 
+MAX_FRAME_CLASSES = 8  # PSN_LK_MAX_FRAME_CLASSES
+
+
+class LkFrameClass(ctypes.Structure):  # psn_lk_frame_class: a source size and its ring slots
+    _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("ring_slots", ctypes.c_int)]
+
+
 class GridFastParams(ctypes.Structure):
     _fields_ = [
         ("threshold", ctypes.c_int),
@@ -257,6 +264,13 @@ def load(path: str | None = None):
         L.psn_lk_create_scaled.argtypes = [ip, ip, ip, ctypes.c_double, ip, ip, ctypes.POINTER(vp)]
         L.psn_lk_source_size.argtypes = [vp, ctypes.POINTER(ip), ctypes.POINTER(ip)]
         L.psn_lk_scale.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+    pip = ctypes.POINTER(ip)
+    L.psn_lk_create_classes.argtypes = [ip, ctypes.POINTER(LkFrameClass), ip, ctypes.c_double, ip, ctypes.POINTER(vp)]
+    L.psn_lk_num_classes.argtypes = [vp]
+    L.psn_lk_slot_class.argtypes = [vp, ip, pip]
+    L.psn_lk_class_slots.argtypes = [vp, ip, pip, pip]
+    L.psn_lk_class_source_size.argtypes = [vp, ip, pip, pip]
+    L.psn_lk_class_level_size.argtypes = [vp, ip, ip, pip, pip]
     L.psn_lk_destroy.argtypes = [vp]
     L.psn_lk_destroy.restype = None
     L.psn_lk_last_error.argtypes = [vp]

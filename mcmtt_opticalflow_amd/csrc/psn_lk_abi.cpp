@@ -222,12 +222,19 @@ int psn_lk_resize_plan(int src, int dst, int *ofs, int16_t *coef, int is_x) {
     return PSN_LK_OK;
 }
 
-// The context of psn_lk_create (src = LK size) and psn_lk_create_scaled.
-static int create_impl(int device, int src_w, int src_h, double scale, int width, int height, int ring_slots,
-                       int max_level_cap, psn_lk_ctx **out) {
-    if (!out || width <= 0 || height <= 0 || ring_slots <= 0 || max_level_cap < 0 ||
+// The context of psn_lk_create_classes; psn_lk_create (scale 1.0) and
+// psn_lk_create_scaled are its one-class cases.
+static int create_impl(int device, const psn_lk_frame_class *cls, int ncls, double scale, int max_level_cap,
+                       psn_lk_ctx **out) {
+    if (!out || !cls || ncls < 1 || ncls > PSN_LK_MAX_FRAME_CLASSES || max_level_cap < 0 ||
         max_level_cap > psn::kPyrMaxTop)
         return PSN_LK_ERR_ARG;
+    int lk_w[PSN_LK_MAX_FRAME_CLASSES], lk_h[PSN_LK_MAX_FRAME_CLASSES], user_slots = 0;
+    for (int k = 0; k < ncls; k++) {
+        if (cls[k].ring_slots <= 0 || user_slots > INT32_MAX / 2 - cls[k].ring_slots) return PSN_LK_ERR_ARG;
+        if (psn_lk_scaled_size(cls[k].width, cls[k].height, scale, &lk_w[k], &lk_h[k])) return PSN_LK_ERR_ARG;
+        user_slots += cls[k].ring_slots;
+    }
     // the pyramid tiles' LDS plan (guarded at build time for every top level:
     // psn::pyr_tiles_fit; kept here so a context never launches past the CU's LDS)
     if (psn::kStScratchBytes + psn::pyr_lds_bytes(max_level_cap, psn::pyr_tile_edge(max_level_cap)) > psn::kMaxLdsBytes)
@@ -236,15 +243,27 @@ static int create_impl(int device, int src_w, int src_h, double scale, int width
     psn_lk_ctx *c = new (std::nothrow) psn_lk_ctx();
     if (!c) return PSN_LK_ERR_NOMEM;
     c->device = device;
-    c->cfg.width = width;
-    c->cfg.height = height;
-    c->src_w = src_w;
-    c->src_h = src_h;
+    c->cfg.width = lk_w[0];
+    c->cfg.height = lk_h[0];
     c->scale = scale;
-    c->rz = src_w != width || src_h != height;
-    c->cfg.user_slots = ring_slots;
-    c->cfg.nslots = ring_slots + 2;
+    c->cfg.user_slots = user_slots;
+    c->cfg.nslots = user_slots + 2;
     c->cfg.nlevels = max_level_cap + 1;
+    c->fcls.resize((size_t)ncls);
+    c->slot_fcls.assign((size_t)c->cfg.nslots, 0);
+    for (int k = 0, first = 0; k < ncls; first += cls[k++].ring_slots) {
+        psn_lk_ctx::FrameClass &f = c->fcls[(size_t)k];
+        f.src_w = cls[k].width;
+        f.src_h = cls[k].height;
+        f.w = lk_w[k];
+        f.h = lk_h[k];
+        f.rz = f.src_w != f.w || f.src_h != f.h;
+        f.first_slot = first;
+        f.nslots = cls[k].ring_slots;
+        for (int s = 0; s < f.nslots; s++) c->slot_fcls[(size_t)(first + s)] = k;
+        if (ncls > 1) c->cfg.cls[k] = psn::PlanFrameClass{f.w, f.h, f.first_slot, f.nslots};
+    }
+    c->cfg.ncls = ncls > 1 ? ncls : 0;  // (one class: the planner's width x height over every slot)
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
@@ -272,38 +291,58 @@ static int create_impl(int device, int src_w, int src_h, double scale, int width
         if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess) return fail(PSN_LK_ERR_HIP);
     c->copy_stream = c->copy_streams[0];
     // slot layout: levels back to back, rows padded to 256 B (one HBM burst / 4 x 64-B lines)
-    size_t slot_bytes = 0;
-    std::vector<size_t> lv_off(c->cfg.nlevels);
-    std::vector<int> lw(c->cfg.nlevels), lh(c->cfg.nlevels), lp(c->cfg.nlevels);
-    {
-        int w = width, h = height;
+    // per frame class
+    for (psn_lk_ctx::FrameClass &f : c->fcls) {
+        size_t slot_bytes = 0;
+        int w = f.w, h = f.h;
         for (int l = 0; l < c->cfg.nlevels; l++) {
-            lw[l] = w;
-            lh[l] = h;
-            lp[l] = (w + 255) & ~255;
-            lv_off[l] = slot_bytes;
-            slot_bytes += (size_t)lp[l] * h;
+            f.ring.w[l] = w;
+            f.ring.h[l] = h;
+            f.ring.pitch[l] = (w + 255) & ~255;
+            f.ring.off[l] = (long long)slot_bytes;
+            slot_bytes += (size_t)f.ring.pitch[l] * h;
             w = (w + 1) / 2;
             h = (h + 1) / 2;
         }
+        f.ring.slot_bytes = (long long)((slot_bytes + 4095) & ~(size_t)4095);
     }
-    slot_bytes = (slot_bytes + 4095) & ~(size_t)4095;
+    // Places in d_pyr. A kernel finds a slot at base + slot * slot_bytes of its
+    // class, and class 0 owns the user slots [0, n0) and the scratch slots
+    // [user_slots, user_slots + 2): its stride spans all nslots slot numbers, and
+    // the other classes' slots lie in the gap between its user and its scratch
+    // slots where they fit (always, when no class is larger than class 0), else
+    // behind the scratch slots. One class: the nslots slots back to back.
+    std::vector<size_t> place(c->fcls.size(), 0);
+    size_t pyr_bytes = 0;
+    {
+        const size_t sb0 = (size_t)c->fcls[0].ring.slot_bytes;
+        size_t gap = sb0 * c->fcls[0].nslots;
+        const size_t gap_end = sb0 * c->cfg.user_slots;
+        pyr_bytes = sb0 * c->cfg.nslots;
+        for (size_t k = 1; k < c->fcls.size(); k++) {
+            const size_t need = (size_t)c->fcls[k].ring.slot_bytes * c->fcls[k].nslots;
+            size_t &at = gap + need <= gap_end ? gap : pyr_bytes;
+            place[k] = at;
+            at += need;
+        }
+    }
     // +256 B slack: the LK kernel's aligned dword staging loads may read up to
     // 3 bytes past the last row of a level
-    if (hipMalloc(&c->d_pyr, slot_bytes * c->cfg.nslots + 256) != hipSuccess) return fail(PSN_LK_ERR_NOMEM);
-    if (hipMemset(c->d_pyr, 0, slot_bytes * c->cfg.nslots + 256) != hipSuccess) return fail(PSN_LK_ERR_HIP);
-    c->ring.base = c->d_pyr;
-    c->ring.slot_bytes = (long long)slot_bytes;
-    for (int l = 0; l < c->cfg.nlevels; l++) {
-        c->ring.off[l] = (long long)lv_off[l];
-        c->ring.w[l] = lw[l];
-        c->ring.h[l] = lh[l];
-        c->ring.pitch[l] = lp[l];
+    if (hipMalloc(&c->d_pyr, pyr_bytes + 256) != hipSuccess) return fail(PSN_LK_ERR_NOMEM);
+    if (hipMemset(c->d_pyr, 0, pyr_bytes + 256) != hipSuccess) return fail(PSN_LK_ERR_HIP);
+    for (size_t k = 0; k < c->fcls.size(); k++) {
+        psn_lk_ctx::FrameClass &f = c->fcls[k];
+        // (an address below d_pyr for a class whose first slot is not 0: never dereferenced without its slot term)
+        f.ring.base = (uint8_t *)((uintptr_t)c->d_pyr + place[k] - (uintptr_t)f.ring.slot_bytes * (uintptr_t)f.first_slot);
     }
     c->h_slots.assign((size_t)c->cfg.nslots * psn::kMaxLevels, LevelDev{nullptr, 0, 0, 0, 0});
-    for (int s = 0; s < c->cfg.nslots; s++)
+    for (int s = 0; s < c->cfg.nslots; s++) {
+        const psn::RingGeo &r = c->class_of(s).ring;
         for (int l = 0; l < c->cfg.nlevels; l++)
-            c->h_slots[(size_t)s * psn::kMaxLevels + l] = LevelDev{c->d_pyr + slot_bytes * s + lv_off[l], lw[l], lh[l], lp[l], 0};
+            c->h_slots[(size_t)s * psn::kMaxLevels + l] =
+                LevelDev{(uint8_t *)((uintptr_t)r.base + (uintptr_t)r.slot_bytes * (uintptr_t)s + (uintptr_t)r.off[l]), r.w[l],
+                         r.h[l], r.pitch[l], 0};
+    }
     if (hipMalloc(&c->d_slots, sizeof(LevelDev) * c->h_slots.size()) != hipSuccess) return fail(PSN_LK_ERR_NOMEM);
     if (hipMemcpy(c->d_slots, c->h_slots.data(), sizeof(LevelDev) * c->h_slots.size(), hipMemcpyHostToDevice) != hipSuccess)
         return fail(PSN_LK_ERR_HIP);
@@ -312,7 +351,10 @@ static int create_impl(int device, int src_w, int src_h, double scale, int width
     c->d_stage.assign(c->cfg.nslots, nullptr);
     c->stage_cap.assign(c->cfg.nslots, 0);
     if (c->slots.init(c->cfg.nslots, &c->err)) return fail(PSN_LK_ERR_HIP);
-    if (c->rz) {
+    for (size_t k = 0; k < c->fcls.size(); k++) {
+        psn_lk_ctx::FrameClass &f = c->fcls[k];
+        if (!f.rz) continue;
+        const int width = f.w, height = f.h, src_w = f.src_w, src_h = f.src_h;
         // the resize tables, computed once, and one gray plane per slot on the ring's 256-B pitch
         std::vector<int> ofs((size_t)std::max(width, height));
         std::vector<int16_t> coef(2 * ofs.size());
@@ -326,35 +368,65 @@ static int create_impl(int device, int src_w, int src_h, double scale, int width
                 t[n + i] = (int)((uint32_t)(uint16_t)coef[2 * i] | ((uint32_t)(uint16_t)coef[2 * i + 1] << 16));
             }
         }
-        if (hipMalloc(&c->d_rz_tab, tab.size() * sizeof(int)) != hipSuccess) return fail(PSN_LK_ERR_NOMEM);
-        if (hipMemcpy(c->d_rz_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+        if (hipMalloc(&f.d_rz_tab, tab.size() * sizeof(int)) != hipSuccess) return fail(PSN_LK_ERR_NOMEM);
+        if (hipMemcpy(f.d_rz_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
             return fail(PSN_LK_ERR_HIP);
-        c->gray_pitch = (width + 255) & ~255;
-        const size_t bytes = (size_t)c->gray_pitch * height * c->cfg.nslots;
-        if (hipMalloc(&c->d_gray, bytes) != hipSuccess) return fail(PSN_LK_ERR_NOMEM);
-        if (hipMemset(c->d_gray, 0, bytes) != hipSuccess) return fail(PSN_LK_ERR_HIP);
+        f.gray_pitch = (width + 255) & ~255;
+        // (class 0: planes for its scratch slots too, as psn_lk_ctx::class_index counts them)
+        const size_t bytes = (size_t)f.gray_pitch * height * (f.nslots + (k == 0 ? 2 : 0));
+        if (hipMalloc(&f.d_gray, bytes) != hipSuccess) return fail(PSN_LK_ERR_NOMEM);
+        if (hipMemset(f.d_gray, 0, bytes) != hipSuccess) return fail(PSN_LK_ERR_HIP);
     }
     *out = c;
     return PSN_LK_OK;
 }
 
 int psn_lk_create(int device, int width, int height, int ring_slots, int max_level_cap, psn_lk_ctx **out) {
-    return create_impl(device, width, height, 1.0, width, height, ring_slots, max_level_cap, out);
+    const psn_lk_frame_class one{width, height, ring_slots};
+    return create_impl(device, &one, 1, 1.0, max_level_cap, out);
 }
 
 int psn_lk_create_scaled(int device, int width, int height, double scale, int ring_slots, int max_level_cap,
                          psn_lk_ctx **out) {
-    int lw = 0, lh = 0;
-    if (psn_lk_scaled_size(width, height, scale, &lw, &lh)) return PSN_LK_ERR_ARG;
-    return create_impl(device, width, height, scale, lw, lh, ring_slots, max_level_cap, out);
+    const psn_lk_frame_class one{width, height, ring_slots};
+    return create_impl(device, &one, 1, scale, max_level_cap, out);
 }
 
-int psn_lk_source_size(psn_lk_ctx *c, int *w, int *h) {
-    if (!c) return PSN_LK_ERR_ARG;
-    if (w) *w = c->src_w;
-    if (h) *h = c->src_h;
+int psn_lk_create_classes(int device, const psn_lk_frame_class *cls, int ncls, double scale, int max_level_cap,
+                          psn_lk_ctx **out) {
+    return create_impl(device, cls, ncls, scale, max_level_cap, out);
+}
+
+int psn_lk_num_classes(psn_lk_ctx *c) { return c ? (int)c->fcls.size() : PSN_LK_ERR_ARG; }
+
+int psn_lk_slot_class(psn_lk_ctx *c, int slot, int *cls) {
+    if (!c || !cls || slot < 0 || slot >= c->cfg.nslots) return PSN_LK_ERR_ARG;
+    *cls = c->slot_fcls[(size_t)slot];
     return PSN_LK_OK;
 }
+
+int psn_lk_class_slots(psn_lk_ctx *c, int cls, int *first_slot, int *nslots) {
+    if (!c || cls < 0 || cls >= (int)c->fcls.size()) return PSN_LK_ERR_ARG;
+    if (first_slot) *first_slot = c->fcls[(size_t)cls].first_slot;
+    if (nslots) *nslots = c->fcls[(size_t)cls].nslots;
+    return PSN_LK_OK;
+}
+
+int psn_lk_class_source_size(psn_lk_ctx *c, int cls, int *w, int *h) {
+    if (!c || cls < 0 || cls >= (int)c->fcls.size()) return PSN_LK_ERR_ARG;
+    if (w) *w = c->fcls[(size_t)cls].src_w;
+    if (h) *h = c->fcls[(size_t)cls].src_h;
+    return PSN_LK_OK;
+}
+
+int psn_lk_class_level_size(psn_lk_ctx *c, int cls, int level, int *w, int *h) {
+    if (!c || cls < 0 || cls >= (int)c->fcls.size() || level < 0 || level >= c->cfg.nlevels) return PSN_LK_ERR_ARG;
+    if (w) *w = c->fcls[(size_t)cls].ring.w[level];
+    if (h) *h = c->fcls[(size_t)cls].ring.h[level];
+    return PSN_LK_OK;
+}
+
+int psn_lk_source_size(psn_lk_ctx *c, int *w, int *h) { return psn_lk_class_source_size(c, 0, w, h); }
 
 int psn_lk_scale(psn_lk_ctx *c, double *s) {
     if (!c || !s) return PSN_LK_ERR_ARG;
@@ -395,8 +467,11 @@ void psn_lk_destroy(psn_lk_ctx *c) {
     c->lg_retired.clear();
     for (void *p : {(void *)c->d_samples, (void *)c->d_ctr, (void *)c->d_pyr, (void *)c->d_slots, (void *)c->d_src, (void *)c->d_prev, (void *)c->d_next,
                     (void *)c->d_err, (void *)c->d_status, (void *)c->d_gf_kp, (void *)c->d_gf_cnt, (void *)c->d_gf_xy,
-                    (void *)c->d_gf_oc, (void *)c->d_gf_ot, (void *)c->d_gray, (void *)c->d_rz_tab})
+                    (void *)c->d_gf_oc, (void *)c->d_gf_ot})
         if (p) (void)hipFree(p);
+    for (const psn_lk_ctx::FrameClass &f : c->fcls)
+        for (void *p : {(void *)f.d_gray, (void *)f.d_rz_tab})
+            if (p) (void)hipFree(p);
     for (void *p : {(void *)c->d_hist_rects, (void *)c->d_hist_counts})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)c->h_hist_rects, (void *)c->h_hist_counts})
@@ -526,10 +601,7 @@ int psn_lk_timing_slides(psn_lk_ctx *c, int cap, int *wgs, int *n) {
 }
 
 int psn_lk_level_size(psn_lk_ctx *c, int level, int *w, int *h) {
-    if (!c || level < 0 || level >= c->cfg.nlevels) return PSN_LK_ERR_ARG;
-    if (w) *w = c->h_slots[level].w;
-    if (h) *h = c->h_slots[level].h;
-    return PSN_LK_OK;
+    return psn_lk_class_level_size(c, 0, level, w, h);
 }
 
 // One standalone pyramid launch of `slot` on stream s, after the resize of a
@@ -567,22 +639,23 @@ static psn::ResizeArgs resize_args(const psn_lk_ctx *c, int slot, const uint8_t 
     r.src = dev;
     r.src_stride = stride;
     r.channels = channels;
-    r.sw = c->src_w;
-    r.sh = c->src_h;
-    r.dst = c->d_gray + (size_t)slot * c->gray_pitch * c->cfg.height;
-    r.dst_pitch = c->gray_pitch;
-    r.dw = c->cfg.width;
-    r.dh = c->cfg.height;
-    r.xofs = c->d_rz_tab;
-    r.xcoef = (const uint32_t *)(c->d_rz_tab + c->cfg.width);
-    r.yofs = c->d_rz_tab + 2 * (size_t)c->cfg.width;
-    r.ycoef = (const uint32_t *)(c->d_rz_tab + 2 * (size_t)c->cfg.width + c->cfg.height);
+    const psn_lk_ctx::FrameClass &f = c->class_of(slot);
+    r.sw = f.src_w;
+    r.sh = f.src_h;
+    r.dst = f.d_gray + (size_t)c->class_index(slot) * f.gray_pitch * f.h;
+    r.dst_pitch = f.gray_pitch;
+    r.dw = f.w;
+    r.dh = f.h;
+    r.xofs = f.d_rz_tab;
+    r.xcoef = (const uint32_t *)(f.d_rz_tab + f.w);
+    r.yofs = f.d_rz_tab + 2 * (size_t)f.w;
+    r.ycoef = (const uint32_t *)(f.d_rz_tab + 2 * (size_t)f.w + f.h);
     return r;
 }
 
 // Resize (a scaled context) and pyramid build of `slot` from a source-size device frame, on stream s.
 static int ingest_build(psn_lk_ctx *c, int slot, const uint8_t *dev, int stride, int channels, hipStream_t s) {
-    if (!c->rz) return launch_build(c, build_args(c, slot, dev, stride, channels), s, slot);
+    if (!c->class_of(slot).rz) return launch_build(c, build_args(c, slot, dev, stride, channels), s, slot);
     const psn::ResizeArgs r = resize_args(c, slot, dev, stride, channels);
     return launch_build(c, build_args(c, slot, r.dst, r.dst_pitch, 1), s, slot, &r);
 }
@@ -597,6 +670,12 @@ static int launch_resize(psn_lk_ctx *c, const psn::ResizeArgs &r, hipStream_t s)
     return psn::timer_end(c, c->t_push, s, ti);
 }
 
+// The width of the frames pushed into `slot` (its class's source width; class 0's
+// for a slot that check_user_slot refuses next).
+static int push_width(const psn_lk_ctx *c, int slot) {
+    return c->fcls[slot >= 0 && slot < c->cfg.user_slots ? (size_t)c->slot_fcls[(size_t)slot] : 0].src_w;
+}
+
 // A push goes to a slot of the user ring.
 static int check_user_slot(psn_lk_ctx *c, int slot) {
     if (slot < 0 || slot >= c->cfg.user_slots) return set_err(c, PSN_LK_ERR_SLOT, "slot %d out of range", slot);
@@ -608,7 +687,7 @@ static int push_device_impl(psn_lk_ctx *c, int slot, const uint8_t *dev, int str
                             bool lk_frame = false) {
     int rc = flush_pending(c);  // at most one deferred build
     if (rc) return rc;
-    const bool rz = c->rz && !lk_frame;
+    const bool rz = c->class_of(slot).rz && !lk_frame;
     psn::ResizeArgs r{};
     if (rz) r = resize_args(c, slot, dev, stride, channels);
     const psn::PyrBuildArgs a = rz ? build_args(c, slot, r.dst, r.dst_pitch, 1) : build_args(c, slot, dev, stride, channels);
@@ -661,25 +740,25 @@ static int push_jpeg(psn_lk_ctx *c, const int *slots, const uint8_t *const *jpeg
         if ((rc = psn_jpeg_create(c->device, &c->jpeg))) return set_err(c, rc, "psn_jpeg_create");
         psn_jpeg_set_stream(c->jpeg, c->ingest_stream);
     }
-    const size_t row = (size_t)c->src_w * 3;
+    // (each frame has its slot's class's source size: the callers checked)
     for (int i = 0; i < n; i++)
-        if ((rc = ensure_stage(c, slots[i], row * c->src_h))) return rc;
+        if ((rc = ensure_stage(c, slots[i], (size_t)c->class_of(slots[i]).src_w * 3 * c->class_of(slots[i]).src_h))) return rc;
     psn_jpeg_item items[PSN_JPEG_MAX_BATCH];
     for (int i = 0; i < n; i++) {
         if ((rc = c->slots.wait_free(slots[i], c->ingest_stream))) return rc;
         // the slot's previous build may still read d_stage[slot] (an async push builds
         // on either ingest stream): the decode overwrites it only after that build
         if ((rc = c->slots.wait_prev_build(slots[i], c->ingest_stream))) return rc;
-        items[i] = {jpeg[i], len[i], c->d_stage[slots[i]], (int)row};
+        items[i] = {jpeg[i], len[i], c->d_stage[slots[i]], c->class_of(slots[i]).src_w * 3};
     }
     rc = batch ? psn_jpeg_decode_batch_device(c->jpeg, items, n)
                : psn_jpeg_decode_device(c->jpeg, items[0].data, items[0].len, items[0].d_bgr, items[0].stride);
     if (rc) return set_err(c, rc, "JPEG decode: %s", psn_jpeg_last_error(c->jpeg));
     for (int i = 0; i < n; i++) {
-        const int slot = slots[i];
+        const int slot = slots[i], row = c->class_of(slot).src_w * 3;
         c->filled[slot] = 1;
-        c->color_src[slot] = {c->d_stage[slot], (int)row, 3, false, 0};
-        if ((rc = ingest_build(c, slot, c->d_stage[slot], (int)row, 3, c->ingest_stream))) return rc;
+        c->color_src[slot] = {c->d_stage[slot], row, 3, false, 0};
+        if ((rc = ingest_build(c, slot, c->d_stage[slot], row, 3, c->ingest_stream))) return rc;
     }
     return PSN_LK_OK;
 }
@@ -690,7 +769,8 @@ int psn_lk_push_frame_jpeg(psn_lk_ctx *c, int slot, const uint8_t *jpeg, size_t 
     int w = 0, h = 0;
     const int rc = psn_jpeg_info(jpeg, len, &w, &h, nullptr);
     if (rc) return set_err(c, rc, "JPEG headers");
-    if (w != c->src_w || h != c->src_h) return set_err(c, PSN_LK_ERR_ARG, "JPEG %dx%d, context %dx%d", w, h, c->src_w, c->src_h);
+    const psn_lk_ctx::FrameClass &f = c->class_of(slot);
+    if (w != f.src_w || h != f.src_h) return set_err(c, PSN_LK_ERR_ARG, "JPEG %dx%d, context %dx%d", w, h, f.src_w, f.src_h);
     return push_jpeg(c, &slot, &jpeg, &len, 1, false);
 }
 
@@ -705,8 +785,9 @@ int psn_lk_push_frames_jpeg(psn_lk_ctx *c, const int *slots, const uint8_t *cons
         int w = 0, h = 0;
         const int rc = psn_jpeg_info(jpeg[i], len[i], &w, &h, nullptr);
         if (rc) return set_err(c, rc, "item %d: JPEG headers", i);
-        if (w != c->src_w || h != c->src_h)
-            return set_err(c, PSN_LK_ERR_ARG, "item %d: JPEG %dx%d, context %dx%d", i, w, h, c->src_w, c->src_h);
+        const psn_lk_ctx::FrameClass &f = c->class_of(slots[i]);
+        if (w != f.src_w || h != f.src_h)
+            return set_err(c, PSN_LK_ERR_ARG, "item %d: JPEG %dx%d, context %dx%d", i, w, h, f.src_w, f.src_h);
     }
     return push_jpeg(c, slots, jpeg, len, n, true);
 }
@@ -728,12 +809,13 @@ int psn_lk_jpeg_batch_stats(psn_lk_ctx *c, int item, struct psn_jpeg_stats *out)
 }
 
 int psn_lk_push_frame_async(psn_lk_ctx *c, int slot, const uint8_t *host, int stride, int channels) {
-    if (!c || !host || (channels != 1 && channels != 3) || stride < c->src_w * channels) return PSN_LK_ERR_ARG;
+    if (!c || !host || (channels != 1 && channels != 3) || stride < push_width(c, slot) * channels) return PSN_LK_ERR_ARG;
     if (check_user_slot(c, slot)) return PSN_LK_ERR_SLOT;
     HIPCHK(c, hipSetDevice(c->device));
     int rc = flush_pending(c);
     if (rc) return rc;
-    const size_t row = (size_t)c->src_w * channels, need = row * c->src_h;
+    const int src_h = c->class_of(slot).src_h;
+    const size_t row = (size_t)c->class_of(slot).src_w * channels, need = row * src_h;
     if ((rc = ensure_stage(c, slot, need))) return rc;
     hipStream_t s = c->ingest_streams[c->ingest_rr++ % psn_lk_ctx::kIngestStreams];
     hipStream_t cs = c->copy_streams[c->copy_rr++ % psn_lk_ctx::kCopyStreams];
@@ -745,7 +827,7 @@ int psn_lk_push_frame_async(psn_lk_ctx *c, int slot, const uint8_t *host, int st
     if ((size_t)stride == row)  // contiguous rows: one linear copy (the DMA engine's fast path)
         HIPCHK(c, hipMemcpyAsync(c->d_stage[slot], host, need, hipMemcpyHostToDevice, cs));
     else
-        HIPCHK(c, hipMemcpy2DAsync(c->d_stage[slot], row, host, stride, row, c->src_h, hipMemcpyHostToDevice, cs));
+        HIPCHK(c, hipMemcpy2DAsync(c->d_stage[slot], row, host, stride, row, src_h, hipMemcpyHostToDevice, cs));
     HIPCHK(c, hipEventRecord(c->slots.copy_done(slot), cs));
     rc = c->slots.wait_free(slot, s);
     if (rc) return rc;
@@ -756,7 +838,7 @@ int psn_lk_push_frame_async(psn_lk_ctx *c, int slot, const uint8_t *host, int st
 }
 
 int psn_lk_push_frame_device(psn_lk_ctx *c, int slot, const uint8_t *dev, int stride, int channels) {
-    if (!c || !dev || (channels != 1 && channels != 3) || stride < c->src_w * channels) return PSN_LK_ERR_ARG;
+    if (!c || !dev || (channels != 1 && channels != 3) || stride < push_width(c, slot) * channels) return PSN_LK_ERR_ARG;
     if (check_user_slot(c, slot)) return PSN_LK_ERR_SLOT;
     HIPCHK(c, hipSetDevice(c->device));
     const int rc = push_device_impl(c, slot, dev, stride, channels);
@@ -766,7 +848,8 @@ int psn_lk_push_frame_device(psn_lk_ctx *c, int slot, const uint8_t *dev, int st
 
 static int push_host_impl(psn_lk_ctx *c, int slot, const uint8_t *host, int stride, int channels,
                           bool lk_frame = false) {
-    const int fw = lk_frame ? c->cfg.width : c->src_w, fh = lk_frame ? c->cfg.height : c->src_h;
+    const psn_lk_ctx::FrameClass &f = c->class_of(slot);
+    const int fw = lk_frame ? f.w : f.src_w, fh = lk_frame ? f.h : f.src_h;
     const size_t row = (size_t)fw * channels, need = row * fh;
     int rc0 = flush_pending(c);  // a deferred build may still read d_src's predecessor frame
     if (rc0) return rc0;
@@ -787,7 +870,7 @@ static int push_host_impl(psn_lk_ctx *c, int slot, const uint8_t *host, int stri
 }
 
 int psn_lk_push_frame(psn_lk_ctx *c, int slot, const uint8_t *host, int stride, int channels) {
-    if (!c || !host || (channels != 1 && channels != 3) || stride < c->src_w * channels) return PSN_LK_ERR_ARG;
+    if (!c || !host || (channels != 1 && channels != 3) || stride < push_width(c, slot) * channels) return PSN_LK_ERR_ARG;
     if (check_user_slot(c, slot)) return PSN_LK_ERR_SLOT;
     HIPCHK(c, hipSetDevice(c->device));
     return push_host_impl(c, slot, host, stride, channels);
@@ -827,7 +910,7 @@ static int launch_plan(psn_lk_ctx *c, const psn::LkLaunchPlan &L, const float *d
                        uint8_t *d_status, float *d_err, const int *d_counts, int count_stride) {
     psn::LkLaunchArgs a{};
     a.slots = c->d_slots;
-    a.ring = c->ring;
+    a.ring = c->fcls[(size_t)L.fcls].ring;
     a.prev = d_prev;
     a.next = d_next;
     a.status = d_status;

@@ -23,19 +23,38 @@
 
 struct psn_lk_ctx {
     int device = 0;
-    // the LK size (ring, pyramids, LK queries, GridFAST rois), the ring and the
-    // kernel-variant overrides: what the launch planner reads
+    // the LK size of class 0 (ring, pyramids, LK queries, GridFAST rois), the ring,
+    // the frame classes' slots and sizes and the kernel-variant overrides: what the
+    // launch planner reads
     psn::PlanCfg cfg;
     // psn_lk_create_scaled: pushed frames have the source size and are resized to
-    // the LK size (PSN_2D_OPTICALFLOW_SCALE); rz = the sizes differ, so every push
-    // runs resize_gray_kernel into the slot's gray plane and the pyramid build
-    // reads that plane as a 1-channel source
-    int src_w = 0, src_h = 0;
+    // the LK size (PSN_2D_OPTICALFLOW_SCALE); FrameClass::rz = the sizes differ, so
+    // every push runs resize_gray_kernel into the slot's gray plane and the pyramid
+    // build reads that plane as a 1-channel source
     double scale = 1.0;
-    bool rz = false;
-    uint8_t *d_gray = nullptr;  // [nslots] planes of height rows, gray_pitch apart
-    int gray_pitch = 0;
-    int *d_rz_tab = nullptr;    // xofs[width] | xcoef[width] | yofs[height] | ycoef[height]
+    // psn_lk_create_classes: per frame class its sizes, its user slots, its slot
+    // layout in d_pyr (the RingGeo its launches receive: base + slot * slot_bytes
+    // holds for the class's own slot numbers, for class 0 the scratch slots too)
+    // and, where it resizes, its tables and gray planes. A one-class context has
+    // one entry and today's layout.
+    struct FrameClass {
+        int src_w = 0, src_h = 0;  // pushed frames
+        int w = 0, h = 0;          // the LK size
+        bool rz = false;
+        int first_slot = 0, nslots = 0;  // its user slots
+        psn::RingGeo ring{};
+        uint8_t *d_gray = nullptr;  // one plane of h rows per slot of the class, gray_pitch apart
+        int gray_pitch = 0;
+        int *d_rz_tab = nullptr;    // xofs[w] | xcoef[w] | yofs[h] | ycoef[h]
+    };
+    std::vector<FrameClass> fcls;
+    std::vector<int> slot_fcls;  // [nslots] the class of every slot (scratch slots: 0)
+    const FrameClass &class_of(int slot) const { return fcls[(size_t)slot_fcls[(size_t)slot]]; }
+    // the slot's place among its class's slots (class 0: the scratch slots follow its user slots)
+    int class_index(int slot) const {
+        const FrameClass &f = class_of(slot);
+        return slot >= cfg.user_slots ? f.nslots + (slot - cfg.user_slots) : slot - f.first_slot;
+    }
     hipStream_t own_stream = nullptr, stream = nullptr;
     // ingest overlap: pyramid builds on their own stream, ordered against the
     // LK launches by per-slot events (psn_lk_slots.h)
@@ -67,7 +86,6 @@ struct psn_lk_ctx {
     psn::PyrBuildArgs pend_args{};
     unsigned *d_ctr = nullptr;  // [2] fused-build work counter + finished workgroups
     int fused_helpers = 0;      // FUSED_HELPERS variant: tile-only workgroups per fused launch
-    psn::RingGeo ring{};        // slot/level geometry passed to the single-tile kernel
     // psn_lk_push_frame_async: per-slot staging buffer of the uploaded frame
     std::vector<uint8_t *> d_stage;
     std::vector<size_t> stage_cap;

@@ -77,8 +77,9 @@ __device__ __forceinline__ int lk_query_point(const LkQueryDev &Q, const int *co
 }
 __host__ __device__ inline unsigned div_magic(int d) { return d > 0 ? ((1u << 22) + (unsigned)d - 1u) / (unsigned)d : 0u; }
 
-// Ring geometry as kernel arguments (every slot has the same level layout):
-// level l of slot s starts at base + s * slot_bytes + off[l].
+// Ring geometry as kernel arguments (every slot of a frame class has the same
+// level layout; a launch serves one class): level l of slot s starts at
+// base + s * slot_bytes + off[l].
 struct RingGeo {
     uint8_t *base;
     long long slot_bytes;

@@ -31,6 +31,8 @@ namespace {
 // The planner's default for the windows the two-wave box build fits
 // (PSN_LK_VARIANT_BX_WAVES 0); DESIGN.md section 8 has the measurement behind it.
 constexpr bool kBxPlanTwoWave = true;
+// A launch group's frame class, packed above its key (box: <= 162, large: <= 192 quads)
+constexpr int kFclsShift = 16;
 // The launches the forward entry fits take it by default (PSN_LK_VARIANT_FW 0): the
 // entry's gains are measured against lk_kernel_bx<10, true> in DESIGN.md section 8.
 // The runtime variant fw=1 plans as if it did not exist.
@@ -50,6 +52,7 @@ struct PlannedQuery {
     bool lg_jr = false;         // + J region in LDS
     int lg_tq = 192;            // + quads per ordered-chain tile
     int cls = kClsLg, key = 0;  // the launch it goes to
+    int fcls = 0;               // the frame class of its two slots
 };
 
 // Row tiles of the row-tiled kernel (window LDS-resident): within the occupancy
@@ -107,7 +110,12 @@ int plan_query(const PlanCfg &c, const char *filled, const psn_lk_query &q, bool
     if (!psn_lk_window_supported(p.win_w, p.win_h))
         return set_err(err, PSN_LK_ERR_UNSUPPORTED, "window %dx%d wider than %d px or above 2^24 px", p.win_w, p.win_h,
                        PSN_LK_MAX_WIN_WIDTH);
-    const int ml = psn_lk_effective_max_level(c.width, c.height, p.win_w, p.win_h, p.max_level);
+    // both pyramids of a query have one geometry: the launch's (its class's RingGeo)
+    pq.fcls = c.slot_class(q.prev_slot);
+    if (c.slot_class(q.next_slot) != pq.fcls)
+        return set_err(err, PSN_LK_ERR_ARG, "slots %d and %d hold frames of different classes (%d, %d)", q.prev_slot,
+                       q.next_slot, pq.fcls, c.slot_class(q.next_slot));
+    const int ml = psn_lk_effective_max_level(c.class_width(pq.fcls), c.class_height(pq.fcls), p.win_w, p.win_h, p.max_level);
     if (ml >= c.nlevels)
         return set_err(err, PSN_LK_ERR_LEVEL_CAP, "query needs %d levels, ring holds %d", ml + 1, c.nlevels);
     int max_count = (p.term_type & PSN_LK_TERM_COUNT) ? std::min(std::max(p.max_count, 0), 100) : 30;
@@ -222,7 +230,7 @@ void merge_sub_queries(std::vector<PlannedQuery> &plan) {
     if (plan.size() <= 1) return;
     auto same_plan = [](const PlannedQuery &x, const PlannedQuery &y) {
         const LkQueryDev &a = x.d, &b = y.d;
-        return x.cls == y.cls && x.key == y.key && a.prev_slot == b.prev_slot && a.next_slot == b.next_slot &&
+        return x.cls == y.cls && x.key == y.key && x.fcls == y.fcls && a.prev_slot == b.prev_slot && a.next_slot == b.next_slot &&
                a.num_pts == b.num_pts && a.win_w == b.win_w && a.win_h == b.win_h &&
                a.max_level == b.max_level && a.max_count == b.max_count && a.flags == b.flags &&
                a.tile_rows == b.tile_rows && a.min_eig == b.min_eig && a.eps2 == b.eps2 && a.dv_w == b.dv_w &&
@@ -265,6 +273,7 @@ void plan_launch(const PlanCfg &c, PlannedQuery *const *grp, int n, int cls, int
                  bool &fuse_given, LkLaunchPlan &L) {
     L.cls = cls;
     L.key = key;
+    L.fcls = n ? grp[0]->fcls : 0;
     int wgs = 0, maxpx = 0, rows_ow = 0, lds_ow = 0, lds = 0;
     for (int i = 0; i < n; i++) {
         const PlannedQuery &pq = *grp[i];
@@ -405,9 +414,13 @@ int plan_call(const PlanCfg &cfg, const psn_lk_query *q, int nq, const char *fil
     // stream, each launch a fraction of the GPU with its own tail: there its
     // windows join the large-window launch (PETS-like boxes: 406 vs 450
     // camera-frames/s with the extra launch)
-    if (std::any_of(plan.begin(), plan.end(), [](const PlannedQuery &pq) { return pq.cls == kClsLg; }))
+    // (per frame class: a large-window launch of another class is another launch anyway)
+    unsigned lg_classes = 0;
+    for (const PlannedQuery &pq : plan)
+        if (pq.cls == kClsLg) lg_classes |= 1u << pq.fcls;
+    if (lg_classes)
         for (PlannedQuery &pq : plan)
-            if (pq.cls == kClsBx && pq.bx_upt == 16) {
+            if (pq.cls == kClsBx && pq.bx_upt == 16 && (lg_classes >> pq.fcls & 1)) {
                 PlannedQuery lq;
                 lq.src = pq.src;
                 int rc = plan_query(cfg, filled, q[pq.src], allow_scratch, lq, err, true);
@@ -419,11 +432,14 @@ int plan_call(const PlanCfg &cfg, const psn_lk_query *q, int nq, const char *fil
         for (int sl : {pq.d.prev_slot, pq.d.next_slot})
             if (std::find(out.used_slots.begin(), out.used_slots.end(), sl) == out.used_slots.end())
                 out.used_slots.push_back(sl);
-    // launch groups: (class, key) in a fixed order, queries in call order
+    // launch groups: (class, key, frame class) in a fixed order, queries in call
+    // order; the frame class rides in the pair's second member above the key
+    auto group_of = [](const PlannedQuery &pq) { return std::pair<int, int>(pq.cls, pq.key + (pq.fcls << kFclsShift)); };
+    auto key_of = [](const std::pair<int, int> &g) { return g.second & ((1 << kFclsShift) - 1); };
     std::vector<std::pair<int, int>> groups;
     std::vector<long long> group_px;
     for (const PlannedQuery &pq : plan) {
-        const std::pair<int, int> g(pq.cls, pq.key);
+        const std::pair<int, int> g = group_of(pq);
         const long long px = (long long)pq.d.win_w * pq.d.win_h * pq.d.num_pts;
         auto it = std::find(groups.begin(), groups.end(), g);
         if (it == groups.end()) {
@@ -438,13 +454,13 @@ int plan_call(const PlanCfg &cfg, const psn_lk_query *q, int nq, const char *fil
     int n = 0;
     auto flush = [&](const std::pair<int, int> &g) {
         out.launches.emplace_back();
-        plan_launch(cfg, grp, n, g.first, g.second, counted, count_stride, fuse_given, out.launches.back());
+        plan_launch(cfg, grp, n, g.first, key_of(g), counted, count_stride, fuse_given, out.launches.back());
         if (out.launches.back().wgs == 0) out.launches.pop_back();
         n = 0;
     };
     for (const auto &g : groups) {
         for (PlannedQuery &pq : plan) {
-            if (pq.cls != g.first || pq.key != g.second) continue;
+            if (group_of(pq) != g) continue;
             grp[n++] = &pq;
             if (n == kMaxQueries) flush(g);
         }
@@ -453,10 +469,11 @@ int plan_call(const PlanCfg &cfg, const psn_lk_query *q, int nq, const char *fil
     for (const LkLaunchPlan &L : out.launches) out.slide_wgs += L.slide_wgs;
     if (!groups.empty()) {
         const size_t dom = (size_t)(std::max_element(group_px.begin(), group_px.end()) - group_px.begin());
-        out.tag = kernel_tag(groups[dom].first, groups[dom].second) + (groups.size() > 1 ? 1000 : 0);
+        const int dcls = groups[dom].first, dkey = key_of(groups[dom]);
+        out.tag = kernel_tag(dcls, dkey) + (groups.size() > 1 ? 1000 : 0);
         bool fw = false;  // (a group's launches share their build, hence their entry)
-        for (const LkLaunchPlan &L : out.launches) fw |= L.cls == groups[dom].first && L.key == groups[dom].second && L.fw;
-        out.entry = entry_tag(groups[dom].first, groups[dom].second, fw) + (groups.size() > 1 ? 1000 : 0);
+        for (const LkLaunchPlan &L : out.launches) fw |= L.cls == dcls && L.key == dkey && L.fw;
+        out.entry = entry_tag(dcls, dkey, fw) + (groups.size() > 1 ? 1000 : 0);
     }
     return PSN_LK_OK;
 }

@@ -30,8 +30,15 @@ inline int set_err(std::string &err, int code, const char *fmt, ...) {
 
 // What the planner knows of a context: the LK frame, the ring and the
 // kernel-variant overrides (psn_lk_debug_set_variant; tests and experiments only).
+// One frame class of a context (psn_lk_create_classes): user slots
+// [first_slot, first_slot + nslots) hold pyramids of width x height (the LK size).
+struct PlanFrameClass {
+    int width = 0, height = 0;
+    int first_slot = 0, nslots = 0;
+};
+
 struct PlanCfg {
-    int width = 0, height = 0;       // the LK size
+    int width = 0, height = 0;       // the LK size (of frame class 0)
     int nlevels = 0;                 // max_level_cap + 1
     int user_slots = 0, nslots = 0;  // user ring + 2 scratch slots (one-shot API)
     int num_cus = 256;               // compute units of the device (launch shaping)
@@ -61,10 +68,24 @@ struct PlanCfg {
     bool force_large = false;
     int lg_lds = 24 * 1024;
     bool lg_jr = true;  // LG_JR: J region of the iterations in LDS where it fits
+    // Frame classes: user slots are numbered class after class, the two scratch
+    // slots (user_slots, user_slots + 1) belong to class 0. ncls == 0: one class
+    // of width x height over every slot.
+    int ncls = 0;
+    PlanFrameClass cls[PSN_LK_MAX_FRAME_CLASSES];
+    // the frame class of `slot` (in [0, nslots))
+    int slot_class(int slot) const {
+        for (int k = 1; k < ncls; k++)
+            if (slot >= cls[k].first_slot && slot < cls[k].first_slot + cls[k].nslots) return k;
+        return 0;
+    }
+    int class_width(int k) const { return ncls ? cls[k].width : width; }
+    int class_height(int k) const { return ncls ? cls[k].height : height; }
 };
 
 // Kernel classes of the planner: each track call's queries go to one launch per
-// class (and per box-kernel build), each launch sized for its own windows.
+// class (per box-kernel build, and per frame class: a launch carries one ring
+// geometry), each launch sized for its own windows.
 enum LkClass { kClsSt = 0, kClsBx = 1, kClsTiled = 2, kClsLg = 3 };
 
 // The kernel a launch runs, as psn_lk_timing_launches reports it.
@@ -97,6 +118,7 @@ struct LkLaunchPlan {
     // the launch may take a deferred pyramid build into its tail (the first
     // single-tile launch of an uncounted call); attaching it is the executor's part
     bool may_fuse = false;
+    int fcls = 0;  // the frame class of its queries' slots: the executor passes that class's RingGeo
 };
 
 // A track call as planned.

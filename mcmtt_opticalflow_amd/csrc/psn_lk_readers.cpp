@@ -28,7 +28,9 @@ void psn_gridfast_default_params(psn_gridfast_params *p) {
 
 // nset sets of rois, set i = nrois[i] rois on ring slot slots[i], all sets'
 // rois consecutive in `rois` and in the outputs; a launch covers up to
-// kGfMaxRois rois of any sets (the shuffle key restarts at 0 per set).
+// kGfMaxRois consecutive rois of any sets of one frame class (the shuffle key
+// restarts at 0 per set): GridFastArgs has one w, h, pitch, so a set of another
+// class than its predecessor's starts a new launch.
 static int gridfast_impl(psn_lk_ctx *c, int nset, const int *slots, const int *nrois, const int *rois,
                          const psn_gridfast_params *pp, uint32_t seed, float *d_xy, int *d_cnt, int *d_tot) {
     psn_gridfast_params p;
@@ -36,13 +38,13 @@ static int gridfast_impl(psn_lk_ctx *c, int nset, const int *slots, const int *n
         p = *pp;
     else
         psn_gridfast_default_params(&p);
-    const int width = c->cfg.width, height = c->cfg.height;
     const int ncell = p.grid_rows * p.grid_cols;
     if (p.grid_rows <= 0 || p.grid_cols <= 0 || ncell > 256 || p.max_total > psn::kGfMaxTotal || p.cap < 0)
         return set_err(c, PSN_LK_ERR_ARG, "gridfast: grid %dx%d, max_total %d, cap %d", p.grid_rows, p.grid_cols,
                        p.max_total, p.cap);
-    if ((width + p.grid_cols - 1) / p.grid_cols - 6 > psn::kGfMaxRegionW)
-        return set_err(c, PSN_LK_ERR_UNSUPPORTED, "gridfast: cell width above %d", psn::kGfMaxRegionW + 6);
+    for (const psn_lk_ctx::FrameClass &f : c->fcls)
+        if ((f.w + p.grid_cols - 1) / p.grid_cols - 6 > psn::kGfMaxRegionW)
+            return set_err(c, PSN_LK_ERR_UNSUPPORTED, "gridfast: cell width above %d", psn::kGfMaxRegionW + 6);
     int nroi = 0;
     std::vector<int> used;  // distinct slots with rois
     for (int i = 0; i < nset; i++) {
@@ -57,17 +59,14 @@ static int gridfast_impl(psn_lk_ctx *c, int nset, const int *slots, const int *n
     int rc = psn::begin_read(c, used.data(), (int)used.size());  // the frames must be in the slots
     if (rc) return rc;
     std::vector<const uint8_t *> roi_img((size_t)nroi);
-    std::vector<int> roi_key((size_t)nroi);
+    std::vector<int> roi_key((size_t)nroi), roi_cls((size_t)nroi);
     for (int i = 0, k = 0; i < nset; i++)
         for (int j = 0; j < nrois[i]; j++, k++) {
             roi_img[k] = c->h_slots[(size_t)slots[i] * psn::kMaxLevels].p;
             roi_key[k] = j;
+            roi_cls[k] = c->slot_fcls[(size_t)slots[i]];
         }
     psn::GridFastArgs a{};
-    const LevelDev &L = c->h_slots[(size_t)used[0] * psn::kMaxLevels];
-    a.w = L.w;
-    a.h = L.h;
-    a.pitch = L.pitch;
     a.threshold = std::min(std::max(p.threshold, 0), 255);
     a.nonmax = p.nonmax ? 1 : 0;
     a.grid_rows = p.grid_rows;
@@ -80,8 +79,15 @@ static int gridfast_impl(psn_lk_ctx *c, int nset, const int *slots, const int *n
     if ((rc = psn::grow_exact(c, c->d_gf_cnt, c->gf_cnt_cap, (size_t)psn::kGfMaxRois * ncell))) return rc;
     a.cell_kp = c->d_gf_kp;
     a.cell_cnt = c->d_gf_cnt;
-    for (int base = 0; base < nroi; base += psn::kGfMaxRois) {
-        const int n = std::min(psn::kGfMaxRois, nroi - base);
+    for (int base = 0, n = 0; base < nroi; base += n) {
+        // the run of rois of one frame class from `base`
+        n = 1;
+        while (n < psn::kGfMaxRois && base + n < nroi && roi_cls[base + n] == roi_cls[base]) n++;
+        const psn::RingGeo &g = c->fcls[(size_t)roi_cls[base]].ring;
+        const int width = g.w[0], height = g.h[0];
+        a.w = width;
+        a.h = height;
+        a.pitch = g.pitch[0];
         a.nroi = n;
         a.out_xy = d_xy + (size_t)base * p.cap * 2;
         a.out_count = d_cnt + base;
@@ -225,14 +231,15 @@ int psn_lk_box_histograms(psn_lk_ctx *c, int nset, const int *slots, const int *
     int bands = 1;
     for (int i = 0, k = 0; i < nset; i++) {
         const psn_lk_ctx::ColorSrc &cs = c->color_src[slots[i]];
+        const int sw = c->class_of(slots[i]).src_w, sh = c->class_of(slots[i]).src_h;
         for (int j = 0; j < nrects[i]; j++, k++) {
             const int *r = rects + 4 * (size_t)k;
             // the four clamps of PSNWhere_Associator3D.cpp:1161-1164, in that order
             long long x = r[0], y = r[1], w = r[2], h = r[3];
             if (x < 0) x = 0;
             if (y < 0) y = 0;
-            if (x + w > c->src_w) w = c->src_w - x;  // (the colour frame has the source size)
-            if (y + h > c->src_h) h = c->src_h - y;
+            if (x + w > sw) w = sw - x;  // (the colour frame has the source size of the slot's class)
+            if (y + h > sh) h = sh - y;
             if (w <= 0 || h <= 0) x = y = w = h = 0;  // an empty crop
             c->h_hist_rects[k] = psn_rgbhist_rect{cs.p, cs.stride, (int)x, (int)y, (int)w, (int)h};
             bands = std::max(bands, psn::rgbhist_bands((int)w, (int)h));

@@ -479,10 +479,19 @@ int psn_t2d_group_create(int device, int ncams, const unsigned *cam_ids, int wid
 int psn_t2d_group_create_scaled(int device, int ncams, const unsigned *cam_ids, int width, int height, double scale,
                                 psn_t2d_group **out) {
     if (!out || ncams <= 0 || !cam_ids) return PSN_LK_ERR_ARG;
+    const std::vector<int> widths((size_t)ncams, width), heights((size_t)ncams, height);
+    return psn_t2d_group_create_sizes(device, ncams, cam_ids, widths.data(), heights.data(), scale, out);
+}
+
+int psn_t2d_group_create_sizes(int device, int ncams, const unsigned *cam_ids, const int *widths, const int *heights,
+                               double scale, psn_t2d_group **out) {
+    if (!out || ncams <= 0 || !cam_ids || !widths || !heights) return PSN_LK_ERR_ARG;
     *out = nullptr;
     psn_t2d_group *g = new (std::nothrow) psn_t2d_group();
     if (!g) return PSN_LK_ERR_NOMEM;
-    const int rc = g->flow.InitializeCameras(std::vector<unsigned>(cam_ids, cam_ids + ncams), width, height, device, scale);
+    const int rc = g->flow.InitializeCameras(std::vector<unsigned>(cam_ids, cam_ids + ncams),
+                                             std::vector<int>(widths, widths + ncams),
+                                             std::vector<int>(heights, heights + ncams), device, scale);
     if (rc) {
         delete g;
         return rc;
@@ -490,6 +499,15 @@ int psn_t2d_group_create_scaled(int device, int ncams, const unsigned *cam_ids, 
     g->iob[0].resize((size_t)ncams);
     g->iob[1].resize((size_t)ncams);
     *out = g;
+    return 0;
+}
+
+int psn_t2d_group_camera_size(psn_t2d_group *g, int cam, int *width, int *height, int *lk_width, int *lk_height) {
+    if (!g || cam < 0 || (size_t)cam >= g->flow.NumCameras()) return PSN_LK_ERR_ARG;
+    if (width) *width = g->flow.Width((size_t)cam);
+    if (height) *height = g->flow.Height((size_t)cam);
+    if (lk_width) *lk_width = g->flow.LkWidth((size_t)cam);
+    if (lk_height) *lk_height = g->flow.LkHeight((size_t)cam);
     return 0;
 }
 
@@ -662,7 +680,7 @@ int psn_t2d_group_appearance(psn_t2d_group *g, unsigned frame_idx, const psn_tra
     rects.resize(4 * total);
     for (size_t c = 0, k = 0; c < C; c++)
         for (int i = 0; i < results[c].num_objects; i++, k++) {
-            const int rc = psn_t2d_appearance_rect(results[c].objects[i].box, g->flow.Width(), g->flow.Height(),
+            const int rc = psn_t2d_appearance_rect(results[c].objects[i].box, g->flow.Width(c), g->flow.Height(c),
                                                    &rects[4 * k]);
             if (rc) return rc;
         }

@@ -21,29 +21,58 @@ int Tracker2DFlow::Initialize(unsigned camID, int width, int height, int device,
 
 int Tracker2DFlow::InitializeCameras(const std::vector<unsigned> &camIDs, int width, int height, int device,
                                      double scale) {
+    return InitializeCameras(camIDs, std::vector<int>(camIDs.size(), width), std::vector<int>(camIDs.size(), height),
+                             device, scale);
+}
+
+int Tracker2DFlow::InitializeCameras(const std::vector<unsigned> &camIDs, const std::vector<int> &widths,
+                                     const std::vector<int> &heights, int device, double scale) {
     Finalize();
-    if (camIDs.empty() || width <= 0 || height <= 0) return PSN_LK_ERR_ARG;
-    if (psn_lk_scaled_size(width, height, scale, &lk_w_, &lk_h_)) {
-        err_ = "scale outside (0, 1] or a scaled frame below 1 px";
-        return PSN_LK_ERR_ARG;
+    const size_t C = camIDs.size();
+    if (C == 0 || widths.size() != C || heights.size() != C) return PSN_LK_ERR_ARG;
+    // frame classes: one per distinct size, in order of first appearance
+    std::vector<psn_lk_frame_class> cls;
+    std::vector<size_t> cam_cls(C), cam_idx(C);  // a camera's class and its place among the class's cameras
+    std::vector<Cam> cams(C);
+    for (size_t c = 0; c < C; c++) {
+        if (widths[c] <= 0 || heights[c] <= 0) return PSN_LK_ERR_ARG;
+        if (psn_lk_scaled_size(widths[c], heights[c], scale, &cams[c].lk_w, &cams[c].lk_h)) {
+            err_ = "scale outside (0, 1] or a scaled frame below 1 px";
+            return PSN_LK_ERR_ARG;
+        }
+        size_t k = 0;
+        while (k < cls.size() && (cls[k].width != widths[c] || cls[k].height != heights[c])) k++;
+        if (k == cls.size()) {
+            if (k == PSN_LK_MAX_FRAME_CLASSES) {
+                err_ = "more than " + std::to_string(PSN_LK_MAX_FRAME_CLASSES) + " distinct frame sizes";
+                return PSN_LK_ERR_ARG;
+            }
+            cls.push_back(psn_lk_frame_class{widths[c], heights[c], 0});
+        }
+        cam_cls[c] = k;
+        cam_idx[c] = (size_t)cls[k].ring_slots / kSlotsPerCam;
+        cls[k].ring_slots += kSlotsPerCam;
     }
-    width_ = width;
-    height_ = height;
     scale_ = scale;
-    const int nslots = (int)camIDs.size() * kSlotsPerCam;
+    const int nslots = (int)C * kSlotsPerCam;
     // full pyramids of every camera's slots; the reference's default maxLevel 3 needs 4 levels
-    // (at scale 1.0 psn_lk_create's context: no resize launch)
-    int rc = psn_lk_create_scaled(device, width, height, scale, nslots, 3, &lk_);
+    // (one size: psn_lk_create_scaled's context, at scale 1.0 psn_lk_create's: no resize launch)
+    int rc = psn_lk_create_classes(device, cls.data(), (int)cls.size(), scale, 3, &lk_);
     if (rc) {
         lk_ = nullptr;
-        err_ = "psn_lk_create_scaled failed (" + std::to_string(rc) + ")";
+        err_ = "psn_lk_create_classes failed (" + std::to_string(rc) + ")";
         return rc;
     }
-    cams_.assign(camIDs.size(), Cam());
-    for (size_t c = 0; c < camIDs.size(); c++) {
+    cams_.swap(cams);
+    for (size_t c = 0; c < C; c++) {
+        int first = 0;
+        psn_lk_class_slots(lk_, (int)cam_cls[c], &first, nullptr);
+        const int base = first + (int)cam_idx[c] * kSlotsPerCam;
         cams_[c].camID = camIDs[c];
-        for (int i = 0; i < kT2dInterval; i++) cams_[c].ring[i] = (int)c * kSlotsPerCam + i;
-        for (int i = 0; i < kT2dStaging; i++) cams_[c].spares[i] = (int)c * kSlotsPerCam + kT2dInterval + i;
+        cams_[c].width = widths[c];
+        cams_[c].height = heights[c];
+        for (int i = 0; i < kT2dInterval; i++) cams_[c].ring[i] = base + i;
+        for (int i = 0; i < kT2dStaging; i++) cams_[c].spares[i] = base + kT2dInterval + i;
         cams_[c].nstaged = 0;
     }
     filled_.assign((size_t)nslots, 0);
@@ -175,7 +204,7 @@ int Tracker2DFlow::DetectFeatures(const std::vector<Detection> &dets, uint32_t s
     features.assign(n, {});
     if (n == 0) return PSN_LK_OK;
     std::vector<int> rois(4 * n), cnt(n), tot(n);
-    for (size_t i = 0; i < n; i++) Roi(dets[i].box, &rois[4 * i]);
+    for (size_t i = 0; i < n; i++) Roi(0, dets[i].box, &rois[4 * i]);
     psn_gridfast_params p;
     psn_gridfast_default_params(&p);
     p.cap = (int)kT2dMaxFeatures;

@@ -8,8 +8,9 @@
 // Track2D_MatchingAndUpdating (:1038-1164) with ResultWithTracker (:1231-1257).
 //
 // One object serves C cameras (CPSNWhere::TrackPeople's per-camera loop,
-// PSNWhere.cpp:257-266): they share one LK context (camera c owns ring slots
-// [c*kSlotsPerCam, c*kSlotsPerCam + kSlotsPerCam)), so a chain step of every
+// PSNWhere.cpp:257-266): they share one LK context (every camera owns
+// kSlotsPerCam ring slots; cameras of equal frame size share a frame class of the
+// context and lie side by side in its slots), so a chain step of every
 // detection of every camera is ONE LK launch, and the forward calls of every
 // tracker of every camera are one launch on a second stream beside the chain.
 #pragma once
@@ -38,6 +39,14 @@ class Tracker2DFlow {
     // (int)(width * scale) x (int)(height * scale), boxes come back with 1 / scale
     int Initialize(unsigned camID, int width, int height, int device, double scale = 1.0);  // one camera
     int InitializeCameras(const std::vector<unsigned> &camIDs, int width, int height, int device, double scale = 1.0);
+    // Cameras with their own frame sizes (the reference sizes every
+    // CPSNWhere_Tracker2D from its own camera, :118-119): cameras of equal size
+    // share a frame class of the LK context (psn_lk_create_classes), classes
+    // numbered in order of first appearance; the GridFAST roi, the windows' level
+    // truncation and the appearance crop follow the camera's own size. More than
+    // PSN_LK_MAX_FRAME_CLASSES distinct sizes: PSN_LK_ERR_ARG.
+    int InitializeCameras(const std::vector<unsigned> &camIDs, const std::vector<int> &widths,
+                          const std::vector<int> &heights, int device, double scale = 1.0);
     void Finalize();
     size_t NumCameras() const { return cams_.size(); }
     psn_lk_ctx *LkContext() const { return lk_; }
@@ -111,8 +120,11 @@ class Tracker2DFlow {
     // The LK ring slot that holds frame frameIdx of camera `cam` (the frames a
     // Run adopted, newest first), or PSN_LK_ERR_SLOT once it has left the ring.
     int SlotOfFrame(size_t cam, unsigned frameIdx, int *slot);
-    int Width() const { return width_; }
-    int Height() const { return height_; }
+    // camera `cam`'s frame (source) size and the size its flow path runs at
+    int Width(size_t cam = 0) const { return cams_[cam].width; }
+    int Height(size_t cam = 0) const { return cams_[cam].height; }
+    int LkWidth(size_t cam = 0) const { return cams_[cam].lk_w; }
+    int LkHeight(size_t cam = 0) const { return cams_[cam].lk_h; }
     double Scale() const { return scale_; }
     // diagnostic: accumulated host microseconds from RunComplete's entry to its
     // phases (copies + next chains enqueued, device done, unpacked, matched, next
@@ -137,6 +149,8 @@ class Tracker2DFlow {
   private:
     struct Cam {  // per-camera state
         unsigned camID = 0;
+        int width = 0, height = 0;  // frame (source) size
+        int lk_w = 0, lk_h = 0;     // the size of its frame class in the LK context: the frame at scale_
         int ring[kT2dInterval];  // slot ids, oldest first; ring[kT2dInterval - 1] = frame t
         // slots outside the ring (multi-camera Run), FIFO: spares[0 .. nstaged) hold
         // staged frames in push order, the rest are free
@@ -170,8 +184,6 @@ class Tracker2DFlow {
     // ---- shared: the context, the cameras' rings and trackers, the last error ----
     psn_lk_ctx *lk_ = nullptr;
     std::vector<Cam> cams_;
-    int width_ = 0, height_ = 0;  // frame (source) size
-    int lk_w_ = 0, lk_h_ = 0;     // the LK context's size: the frame at scale_
     double scale_ = 1.0;
     std::vector<char> filled_;  // per LK slot
     std::string err_;
@@ -226,7 +238,7 @@ class Tracker2DFlow {
     void Chk(hipError_t e, const char *what, int &rc);  // the first HIP error of a sequence: err_ and rc
     static psn_lk_query Query(int prev_slot, int next_slot, size_t first_pt, size_t num_pts);
     static int WindowError(int w, int h);       // the error of a window the LK cannot run, or 0
-    void Roi(const Rect &box, int *roi) const;  // GridFAST's roi of a detection box
+    void Roi(size_t cam, const Rect &box, int *roi) const;  // GridFAST's roi of a detection box of camera `cam`
     template <class Launch>
     int OnForwardStream(int par, Launch launch, hipError_t &recorded);
     int PassLaunch(std::vector<PassCam> &pc, bool gridfast, uint32_t seed);  // chains, then forward

@@ -45,8 +45,8 @@ psn_lk_query Tracker2DFlow::Query(int prev_slot, int next_slot, size_t first_pt,
 }
 
 // cv::Rect((int)x, (int)y, (int)w, (int)h) of the cropped, scaled box (:736)
-void Tracker2DFlow::Roi(const Rect &box, int *roi) const {
-    const Rect r = box.scale(scale_).cropWithSize(lk_w_, lk_h_);
+void Tracker2DFlow::Roi(size_t cam, const Rect &box, int *roi) const {
+    const Rect r = box.scale(scale_).cropWithSize(cams_[cam].lk_w, cams_[cam].lk_h);
     roi[0] = (int)r.x;
     roi[1] = (int)r.y;
     roi[2] = (int)r.w;
@@ -285,7 +285,7 @@ int Tracker2DFlow::PassLaunchChains(std::vector<PassCam> &pc, bool gridfast, uin
             if (!n) continue;
             slots.push_back(cams_[p.cam].ring[kT2dInterval - 1]);
             nrois.push_back((int)n);
-            for (size_t i = 0; i < n; i++) Roi((*p.dets)[i].box, &rois[4 * (p.k0 + i)]);
+            for (size_t i = 0; i < n; i++) Roi(p.cam, (*p.dets)[i].box, &rois[4 * (p.k0 + i)]);
         }
         rc = psn_gridfast_detect_device_sets(lk_, (int)slots.size(), slots.data(), nrois.data(), rois.data(), &gp,
                                              seed, db.d_in, db.d_cnt, db.d_tot);

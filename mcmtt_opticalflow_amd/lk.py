@@ -98,10 +98,71 @@ class LKContext:
         if rc != 0:
             raise PsnLkError(rc, "psn_lk_create" if scale is None else f"psn_lk_create_scaled(scale={scale})")
         self._h = h
+        self._finish(variants)
+
+    def _finish(self, variants):
         self.scale = self.get_scale() if hasattr(self._L, "psn_lk_scale") else 1.0  # (an A/B experiment's older build)
         self.lk_width, self.lk_height = self.level_size(0)
+        if hasattr(self._L, "psn_lk_num_classes"):  # (absent from the A/B experiments' older builds only)
+            n = self._L.psn_lk_num_classes(self._h)
+            self.classes = [self.class_source_size(k) + (self.class_slots(k)[1],) for k in range(n)]
+            self._slot_src = [self.class_source_size(self.slot_class(s)) for s in range(self.ring_slots)]
+        else:
+            self.classes = [(self.width, self.height, self.ring_slots)]
+            self._slot_src = [(self.width, self.height)] * self.ring_slots
         for k, v in (variants or {}).items():
             self.set_variant(k, v)
+
+    @classmethod
+    def with_classes(cls, classes, scale: float | None = None, max_level_cap: int = 3, device: int = 0,
+                     variants: dict | None = None):
+        """One context for frames of several sizes (psn_lk_create_classes): classes =
+        [(width, height, ring_slots), ...] source sizes; user slots are numbered class
+        after class, one scale for all (None = 1.0). width / height / lk_width /
+        lk_height speak of class 0; per class see class_source_size, class_level_size,
+        class_slots, slot_class."""
+        self = cls.__new__(cls)
+        self._L = _lib.load()
+        cl = [tuple(int(v) for v in c) for c in classes]
+        self.width, self.height = cl[0][:2] if cl else (0, 0)
+        self.ring_slots, self.max_level_cap = sum(c[2] for c in cl), max_level_cap
+        arr = (_lib.LkFrameClass * max(len(cl), 1))(*[_lib.LkFrameClass(*c) for c in cl])
+        h = ctypes.c_void_p()
+        rc = self._L.psn_lk_create_classes(device, arr, len(cl), 1.0 if scale is None else float(scale), max_level_cap,
+                                           ctypes.byref(h))
+        if rc != 0:
+            raise PsnLkError(rc, f"psn_lk_create_classes({cl}, scale={scale})")
+        self._h = h
+        self._finish(variants)
+        return self
+
+    def slot_class(self, slot: int) -> int:
+        k = ctypes.c_int()
+        self._check(self._L.psn_lk_slot_class(self._h, slot, ctypes.byref(k)), "slot_class")
+        return k.value
+
+    def class_slots(self, k: int):
+        """(first user slot, user slots) of frame class k."""
+        a, n = ctypes.c_int(), ctypes.c_int()
+        self._check(self._L.psn_lk_class_slots(self._h, k, ctypes.byref(a), ctypes.byref(n)), "class_slots")
+        return a.value, n.value
+
+    def class_source_size(self, k: int):
+        w, h = ctypes.c_int(), ctypes.c_int()
+        self._check(self._L.psn_lk_class_source_size(self._h, k, ctypes.byref(w), ctypes.byref(h)), "class_source_size")
+        return w.value, h.value
+
+    def class_level_size(self, k: int, level: int):
+        w, h = ctypes.c_int(), ctypes.c_int()
+        self._check(self._L.psn_lk_class_level_size(self._h, k, level, ctypes.byref(w), ctypes.byref(h)),
+                    "class_level_size")
+        return w.value, h.value
+
+    def _check_frame(self, slot: int, img):
+        """A frame pushed to `slot` has the source size of the slot's class."""
+        if 0 <= slot < len(self._slot_src) and (img.shape[1], img.shape[0]) != self._slot_src[slot]:
+            raise PsnLkError(-1, f"slot {slot} takes {self._slot_src[slot][0]}x{self._slot_src[slot][1]} frames, "
+                                 f"got {img.shape[1]}x{img.shape[0]}")
 
     def set_variant(self, key: str, value: int):
         """Kernel-variant override (psn_lk_debug_set_variant): tests and experiments only."""
@@ -162,7 +223,7 @@ class LKContext:
     def push_frame(self, slot: int, img: np.ndarray):
         img = np.ascontiguousarray(img, dtype=np.uint8)
         ch = 1 if img.ndim == 2 else img.shape[2]
-        assert img.shape[0] == self.height and img.shape[1] == self.width
+        self._check_frame(slot, img)
         self._check(self._L.psn_lk_push_frame(self._h, slot, img.ctypes.data, img.shape[1] * ch, ch), "push_frame")
 
     def push_frame_async(self, slot: int, img: np.ndarray):
@@ -170,6 +231,7 @@ class LKContext:
         alive and unchanged until sync() (pinned memory makes the copy async)."""
         ch = 1 if img.ndim == 2 else img.shape[2]
         assert img.flags["C_CONTIGUOUS"] and img.dtype == np.uint8
+        self._check_frame(slot, img)
         self._check(self._L.psn_lk_push_frame_async(self._h, slot, img.ctypes.data, img.shape[1] * ch, ch),
                     "push_frame_async")
 
@@ -205,10 +267,12 @@ class LKContext:
         self._check(self._L.psn_lk_push_frame_device(self._h, slot, dev_ptr, stride, channels), "push_frame_device")
 
     def read_level(self, slot: int, level: int) -> np.ndarray:
-        w, h = ctypes.c_int(), ctypes.c_int()
-        self._check(self._L.psn_lk_level_size(self._h, level, ctypes.byref(w), ctypes.byref(h)), "level_size")
-        out = np.empty((h.value, w.value), np.uint8)
-        self._check(self._L.psn_lk_read_level(self._h, slot, level, out.ctypes.data, w.value), "read_level")
+        if len(self.classes) > 1:
+            w, h = self.class_level_size(self.slot_class(slot), level)
+        else:
+            w, h = self.level_size(level)
+        out = np.empty((h, w), np.uint8)
+        self._check(self._L.psn_lk_read_level(self._h, slot, level, out.ctypes.data, w), "read_level")
         return out
 
     def track(self, queries: list[LkQuery], prev_pts: np.ndarray, next_pts: np.ndarray | None = None,

@@ -185,6 +185,8 @@ def load():
                                                 ctypes.c_uint, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(Tracker),
                                                 ip, ctypes.POINTER(ip), ctypes.POINTER(Track2DResult)]
     L.psn_t2d_group_create.argtypes = [ip, ip, vp, ip, ip, ctypes.POINTER(vp)]
+    L.psn_t2d_group_create_sizes.argtypes = [ip, ip, vp, vp, vp, ctypes.c_double, ctypes.POINTER(vp)]
+    L.psn_t2d_group_camera_size.argtypes = [vp, ip] + [ctypes.POINTER(ip)] * 4
     L.psn_t2d_group_destroy.argtypes = [vp]
     L.psn_t2d_group_destroy.restype = None
     L.psn_t2d_group_last_error.argtypes = [vp]
@@ -487,12 +489,44 @@ class Group:
             raise T2dError(rc, "psn_t2d_group_create" if scale is None else
                            f"psn_t2d_group_create_scaled(scale={scale})")
         self._h = h
+        self._finish(len(cam_ids), [(width, height)] * len(cam_ids), scale, max_objects)
+
+    def _finish(self, ncams, sizes, scale, max_objects):
         self.scale = 1.0 if scale is None else float(scale)
-        self.ncams = len(cam_ids)
-        self.width, self.height = width, height
+        self.ncams = ncams
+        self.sizes = [(int(w), int(h)) for w, h in sizes]  # per camera: the size of pushed frames
+        self.width, self.height = self.sizes[0]
         self.results = [ResultBuffers(max_objects, 1) for _ in range(self.ncams)]
         self._res = (Track2DResult * self.ncams)(*[r.r for r in self.results])
         self._keep = None
+
+    @classmethod
+    def with_sizes(cls, sizes, cam_ids, device: int = 0, max_objects: int = 64, scale: float | None = None):
+        """A group whose camera c takes frames of sizes[c] = (width, height)
+        (psn_t2d_group_create_sizes): cameras of equal size share a frame class of the
+        LK context, every camera's LK work still rides in the group's launches."""
+        self = cls.__new__(cls)
+        self._L = load()
+        n = len(cam_ids)
+        if len(sizes) != n:
+            raise ValueError("one size per camera")
+        ids = (ctypes.c_uint * max(n, 1))(*cam_ids)
+        ws = (ctypes.c_int * max(n, 1))(*[int(s[0]) for s in sizes])
+        hs = (ctypes.c_int * max(n, 1))(*[int(s[1]) for s in sizes])
+        h = ctypes.c_void_p()
+        rc = self._L.psn_t2d_group_create_sizes(device, n, ids, ws, hs, 1.0 if scale is None else float(scale),
+                                                ctypes.byref(h))
+        if rc:
+            raise T2dError(rc, f"psn_t2d_group_create_sizes({list(sizes)}, scale={scale})")
+        self._h = h
+        self._finish(n, sizes, scale, max_objects)
+        return self
+
+    def camera_size(self, cam: int):
+        """psn_t2d_group_camera_size -> (width, height, lk_width, lk_height) of camera `cam`."""
+        v = [ctypes.c_int() for _ in range(4)]
+        self._check(self._L.psn_t2d_group_camera_size(self._h, cam, *[ctypes.byref(x) for x in v]), "camera_size")
+        return tuple(x.value for x in v)
 
     def _check(self, rc, what):
         if rc:
@@ -516,6 +550,9 @@ class Group:
         """Asynchronous upload of camera `cam`'s frame t (must stay alive until complete())."""
         assert img.flags["C_CONTIGUOUS"] and img.dtype == np.uint8
         ch = 1 if img.ndim == 2 else img.shape[2]
+        if 0 <= cam < self.ncams and (img.shape[1], img.shape[0]) != self.sizes[cam]:
+            raise T2dError(-1, f"push_frame: camera {cam} takes {self.sizes[cam][0]}x{self.sizes[cam][1]} frames, "
+                               f"got {img.shape[1]}x{img.shape[0]}")
         self._check(self._L.psn_t2d_group_push_frame(self._h, cam, img.ctypes.data, img.shape[1] * ch, ch),
                     "push_frame")
 
