@@ -365,6 +365,10 @@ int psn_lk_timing_slides(psn_lk_ctx *ctx, int cap, int *wgs, int *n);
  *                              2,049 - 2,560 units of 4 px, Tracker2D's 64 x 160)
  *   PSN_LK_VARIANT_ERR_STATUS  0 = PSN_LK_ERR_STATUS_ONLY is honoured by the kernels that
  *                              take it; 1 = the flag is ignored (every launch writes err)
+ *   PSN_LK_VARIANT_BX_PACK     0 = two-wave box launches request one CU slot of LDS
+ *                              (26,624 B) and forward-entry launches two, so either
+ *                              kind fits the holes the other leaves on a CU; 1 = every
+ *                              launch requests its planned layout size
  * Queries are split into one launch per window class (single-tile / box kernel
  * per units-per-thread and tail build / row-tiled / large), each sized for its
  * own windows. */
@@ -382,6 +386,7 @@ int psn_lk_timing_slides(psn_lk_ctx *ctx, int cap, int *wgs, int *n);
 #define PSN_LK_VARIANT_BX_WAVES 12
 #define PSN_LK_VARIANT_FW 13
 #define PSN_LK_VARIANT_ERR_STATUS 14
+#define PSN_LK_VARIANT_BX_PACK 15
 int psn_lk_debug_set_variant(psn_lk_ctx *ctx, int key, int value);
 
 /* Window-sample counter (SURVEY 8(d)'s compute figure): while on, every box-

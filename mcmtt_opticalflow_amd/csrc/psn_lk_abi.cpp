@@ -948,7 +948,7 @@ static int launch_plan(psn_lk_ctx *c, const psn::LkLaunchPlan &L, const float *d
     }
     if (L.cls == psn::kClsBx) {
         a.poison_lds = c->poison_lds ? lds : 0;
-        HIPCHK(c, psn::launch_lk_bx(a, wgs, L.upt, L.notail, L.nt, L.fw, lds, c->stream));
+        HIPCHK(c, psn::launch_lk_bx(a, wgs, L.upt, L.notail, L.nt, L.fw, lds, c->bx_pack, c->stream));
         return PSN_LK_OK;
     }
     if (L.cls == psn::kClsTiled) {
@@ -1127,6 +1127,10 @@ int psn_lk_debug_set_variant(psn_lk_ctx *c, int key, int value) {
         c->cfg.fw = value;
         return PSN_LK_OK;
     case PSN_LK_VARIANT_ERR_STATUS: c->cfg.err_status_ignore = value != 0; return PSN_LK_OK;
+    case PSN_LK_VARIANT_BX_PACK:
+        if (value != 0 && value != 1) return PSN_LK_ERR_ARG;
+        c->bx_pack = value == 0;
+        return PSN_LK_OK;
     default: return PSN_LK_ERR_ARG;
     }
 }

@@ -93,10 +93,16 @@ __global__ __launch_bounds__(NT, bx_waves_per_simd(UPT, NOTAIL, NT)) void lk_ker
 // entry stands in for (kBxFwUPT).
 #define PSN_FW_KERNELS(X) X(kBxFwUPT, true, kBxNT)
 
-hipError_t launch_lk_bx(const LkLaunchArgs &a, int total_wgs, int upt, bool notail, int nt, bool fw, int lds_bytes,
-                        hipStream_t s) {
+hipError_t launch_lk_bx(const LkLaunchArgs &a0, int total_wgs, int upt, bool notail, int nt, bool fw, int planned_lds,
+                        bool pack, hipStream_t s) {
     if (total_wgs <= 0) return hipSuccess;
     const dim3 grid(total_wgs);
+    // The request in CU slots (psn_lk_kernels.h): the kernels lay their window out
+    // from its size alone, so the bytes past the plan are never touched -- POISON_LDS
+    // fills them too, which is how the tests hold that.
+    const int lds_bytes = bx_lds_request(planned_lds, nt, fw, pack);
+    LkLaunchArgs a = a0;
+    if (a.poison_lds) a.poison_lds = lds_bytes;
 #define PSN_BX_LAUNCH(U, NOTAIL, NT)                                                            \
     if (!fw && upt == U && notail == NOTAIL && nt == NT) {                                      \
         hipLaunchKernelGGL((lk_kernel_bx<U, NOTAIL, NT>), grid, dim3(NT), lds_bytes, s, a);     \

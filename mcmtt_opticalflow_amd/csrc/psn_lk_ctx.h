@@ -122,6 +122,7 @@ struct psn_lk_ctx {
     uint8_t *d_status = nullptr;
     size_t d_pts_cap = 0;
     bool poison_lds = false;  // POISON_LDS 1: LK launches fill their LDS with a pattern first
+    bool bx_pack = true;      // BX_PACK 0: two-wave and forward box launches request whole CU slots of LDS
     // the large-window kernel's window-value slots in HBM, one buffer per stream
     // (launches on one stream run in order; launches on different streams may overlap)
     struct LgWs {

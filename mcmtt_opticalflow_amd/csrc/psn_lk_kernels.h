@@ -288,6 +288,26 @@ __host__ __device__ constexpr int bx_waves_per_simd(int upt, bool notail, int nt
     return bx_occupancy(upt, notail, nt) * (nt / 64) / 4;
 }
 constexpr int kBxLdsTarget6 = 160 * 1024 / 6;  // 27,306 B: six workgroups per CU
+// CU slots: the two-wave build and the forward entry run side by side in the
+// Tracker2D pipeline (backward chain launches beside a forward launch), so their
+// LDS requests come from one grid of kBxSlotsPerCu slots of kBxLdsSlot bytes: a
+// two-wave workgroup asks for one slot and a forward workgroup for two, whatever
+// their windows' layouts need, and a retiring workgroup of either kind leaves a
+// hole the other kind fits. The CU hands LDS out in granules (residency, DESIGN.md
+// section 8 round 13: 1,280 B -- 128 to the CU): the planned 25,920 B and 52,416 B
+// of the 64 x 64 and 64 x 160 windows are 21 and 41 of them, so two two-wave
+// workgroups did not fit the hole of a forward one. The slot is 26 KB (21
+// granules; 13 of 2 KB), the forward request 52 KB (42): six and three to a CU as
+// before. A slot of kBxLdsTarget / 2 = 27,136 B is 22 granules and holds only five
+// and two. The 256-thread lk_kernel_bx builds keep their planned requests (0 slots).
+constexpr int kBxLdsSlot = 26 * 1024;  // 26,624 B
+constexpr int kBxSlotsPerCu = 6;
+__host__ __device__ constexpr int bx_lds_slots(int nt, bool fw) { return nt == kBxNT2 ? 1 : fw ? 2 : 0; }
+// the dynamic-LDS request of a launch planned at `planned` bytes: its slots with
+// `pack` (PSN_LK_VARIANT_BX_PACK 0), and a plan above its slots keeps its own size
+__host__ __device__ constexpr int bx_lds_request(int planned, int nt, bool fw, bool pack) {
+    return pack && planned < bx_lds_slots(nt, fw) * kBxLdsSlot ? bx_lds_slots(nt, fw) * kBxLdsSlot : planned;
+}
 __host__ __device__ constexpr int bx_lds_target(int upt, bool notail, int nt = kBxNT) {
     return nt == kBxNT2                        ? kBxLdsTarget6
            : bx_occupancy(upt, notail) == 4 ? 40 * 1024
@@ -455,6 +475,8 @@ static_assert(lg_scr_bytes() + lg_tiles_a_bytes(kLgTQs[0]) <= kMaxLdsBytes &&
 static_assert(kLgJrMaxLds > 0 && kLgJrMaxLds <= kMaxLdsBytes, "PSN_LG_JR_MAX_KB exceeds 160 KB");
 static_assert(kBxMaxLds <= kMaxLdsBytes && kBxLdsTarget <= kBxMaxLds && 2 * kBxMaxLds2 <= kMaxLdsBytes,
               "box-kernel LDS caps exceed 160 KB");
+static_assert(kBxSlotsPerCu * ((kBxLdsSlot + 1279) / 1280 * 1280) <= kMaxLdsBytes && 2 * kBxLdsSlot <= kBxLdsTarget,
+              "the CU's slot grid: six slots of whole LDS granules within 160 KB, a forward request within its target");
 
 constexpr int kStEPTMax = 4;  // window pixels per thread held in registers by the single-tile kernel
 constexpr int kStMaxLds = 150 * 1024;
@@ -476,8 +498,9 @@ hipError_t launch_lk_st(const LkLaunchArgs &a, int total_wgs, int nt, int ept, i
 // (no scalar-tail chain: a build without its per-pixel bookkeeping); nt: the
 // workgroup size (kBxNT, or kBxNT2 for the two-wave build <8, true>); fw: the
 // forward entry lk_kernel_fw of that build (PSN_FW_KERNELS; bx_fw_fits)
+// pack: the request is rounded to the build's CU slots (bx_lds_request)
 hipError_t launch_lk_bx(const LkLaunchArgs &a, int total_wgs, int upt, bool notail, int nt, bool fw, int lds_bytes,
-                        hipStream_t s);
+                        bool pack, hipStream_t s);
 // Large-window kernel (psn_lk_large.hip): `grid` workgroups over a.lk_wgs points.
 hipError_t launch_lk_lg(const LkLaunchArgs &a, int grid, int lds_bytes, int tq, hipStream_t s);
 // Each family's unit raises the dynamic-LDS limit of its own kernels;
