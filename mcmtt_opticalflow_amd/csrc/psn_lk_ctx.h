@@ -18,6 +18,7 @@
 #include "psn_jpeg.h"
 #include "psn_rgbhist.h"
 #include "psn_lk_kernels.h"
+#include "psn_lk_layout.h"
 #include "psn_lk_plan.h"
 #include "psn_lk_slots.h"
 
@@ -37,16 +38,7 @@ struct psn_lk_ctx {
     // holds for the class's own slot numbers, for class 0 the scratch slots too)
     // and, where it resizes, its tables and gray planes. A one-class context has
     // one entry and today's layout.
-    struct FrameClass {
-        int src_w = 0, src_h = 0;  // pushed frames
-        int w = 0, h = 0;          // the LK size
-        bool rz = false;
-        int first_slot = 0, nslots = 0;  // its user slots
-        psn::RingGeo ring{};
-        uint8_t *d_gray = nullptr;  // one plane of h rows per slot of the class, gray_pitch apart
-        int gray_pitch = 0;
-        int *d_rz_tab = nullptr;    // xofs[w] | xcoef[w] | yofs[h] | ycoef[h]
-    };
+    using FrameClass = psn::FrameClass;  // psn_lk_layout.h
     std::vector<FrameClass> fcls;
     std::vector<int> slot_fcls;  // [nslots] the class of every slot (scratch slots: 0)
     const FrameClass &class_of(int slot) const { return fcls[(size_t)slot_fcls[(size_t)slot]]; }
@@ -178,6 +170,14 @@ namespace psn {
 // With a stream `on` of the caller's, that stream waits instead; a slot with no
 // build event is ordered behind the context stream through `order_ev`.
 int begin_read(psn_lk_ctx *c, const int *slots, int n, hipStream_t on = nullptr, hipEvent_t order_ev = nullptr);
+
+// Runs a deferred (fused-mode) build now, as its own launch on the context stream (psn_lk_ingest.cpp).
+int flush_pending(psn_lk_ctx *c);
+
+// Uploads a host frame of `slot`'s source size (lk_frame: of its LK size, no
+// resize) and builds the slot's pyramid; the frame is the caller's again on
+// return. The slot and the device are the caller's to check (psn_lk_ingest.cpp).
+int push_host_impl(psn_lk_ctx *c, int slot, const uint8_t *host, int stride, int channels, bool lk_frame = false);
 
 // Bracket of a timed call on stream s: ti = the call's place in the ring (-1: not timed).
 int timer_begin(psn_lk_ctx *c, psn_lk_ctx::CallTimer &t, hipStream_t s, long &ti);

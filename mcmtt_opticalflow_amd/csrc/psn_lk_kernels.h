@@ -458,6 +458,10 @@ __host__ __device__ constexpr int pyr_lds_bytes(int top, int T) {
 constexpr int kPyrTile = PSN_PYR_TILE;
 constexpr int kPyrTileDeep = 4;
 __host__ __device__ constexpr int pyr_tile_edge(int top) { return top <= 4 ? kPyrTile : kPyrTileDeep; }
+// ... and of a deferred build that runs in an LK launch's tail. It does not
+// follow PSN_PYR_TILE: the tiles share the workgroup's LDS with the LK work, so
+// the edge has to fit the LK launch's LDS budget whatever the standalone build takes.
+constexpr int pyr_tile_edge_fused(int top) { return top <= 4 ? 8 : 4; }
 // Build-time guards (a bad build parameter fails the compile instead of a launch
 // with hipErrorInvalidValue): every top level a context may build, standalone and
 // fused behind the single-tile kernel's scratch, fits the CU's LDS.

@@ -1,6 +1,6 @@
 // The launch planner of a track call (psn_lk_plan.h): which kernel takes which
 // query, and every launch's shape. The executor is track_device_impl
-// (psn_lk_abi.cpp).
+// (psn_lk_track.cpp).
 #include "psn_lk_plan.h"
 
 #include <algorithm>

@@ -1,6 +1,6 @@
 // Gray resize of the ingest path at a reduced optical-flow scale (kernel in
-// psn_resize.hip; the tables and the C ABI, psn_lk_resize_plan /
-// psn_lk_create_scaled of include/psn_lk.h, in psn_lk_abi.cpp).
+// psn_resize.hip; the tables, psn_lk_resize_plan of include/psn_lk.h, in
+// psn_lk_layout.cpp; psn_lk_create_scaled in psn_lk_context.cpp).
 //
 // cvtColor(BGR2GRAY) then cv::resize(gray, ring[slot], Size(w * s, h * s)) of
 // PSNWhere_Tracker2D.cpp:257-262: OpenCV 2.4.6 resize(INTER_LINEAR) for CV_8UC1
