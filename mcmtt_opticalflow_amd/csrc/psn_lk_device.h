@@ -48,8 +48,7 @@ __device__ __forceinline__ int cv_floor(float v) { return (int)floorf(v); }
 //  * otherwise: the per-pixel float products are laid out chain-major in LDS
 //    and each SSE2 lane / scalar tail chain is summed sequentially by one lane.
 
-constexpr unsigned kSatCap = 1u << 30;
-constexpr int kExact = 1 << 24;
+constexpr unsigned kSatCap = 1u << 30;  // (kExact = 2^24: psn_lk_kernels.h)
 
 // Exactness of a float sum of integer terms t in ANY order or chain split:
 // every partial sum is a subset sum, inside [-N, P] (P = sum of the positive

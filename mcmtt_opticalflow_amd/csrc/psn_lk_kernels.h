@@ -161,7 +161,8 @@ __host__ __device__ inline int lk_st_planeB(int w, int h, bool sse) {
 //   dg: Scharr (Ix, Iy) short2 of every level ((h+1) x (w+1));
 //   iw: per level and window pixel {Iw, Ix | Iy << 16} (int2);
 //   r: A products of every level (3 chain-major planes per level); reused by
-//     the double-buffered b products of the iterations and the err plane.
+//     the double-buffered b products of the iterations (sized for a row of
+//     w * h floats as well: the err pass once kept one, and the plans hold).
 constexpr int kStMaxLev = kPyrMaxTop + 1;
 constexpr int kStJMargin = 4;  // J region margin (px) each side; prefetched at the predicted position
 constexpr int kStRiIt = 0, kStRiErr = 64, kStRiTile = 96, kStRiA = 128;           // ints
@@ -193,7 +194,7 @@ __host__ __device__ inline int lk_pat_rs(int w) { return 4 * lk_pat_m(w); }
 //   one-wave layout (ow): the window values IW of every level, then a union
 //     of what only the prologue uses (I patches, Scharr planes, the A-phase
 //     float chain planes RA) and what only the iterations use (the two J
-//     regions JP, the b chain planes / err row R) -- 49.6 KB at 21x21 with 4
+//     regions JP, the b chain planes R) -- 49.6 KB at 21x21 with 4
 //     levels: three workgroups per CU.
 //   overlapped one-wave layout (ow + ovl): no union -- the prologue computes only
 //     the coarsest level's A phase; waves 1-3 compute the finer levels' (I
@@ -482,7 +483,15 @@ static_assert(kBxMaxLds <= kMaxLdsBytes && kBxLdsTarget <= kBxMaxLds && 2 * kBxM
 static_assert(kBxSlotsPerCu * ((kBxLdsSlot + 1279) / 1280 * 1280) <= kMaxLdsBytes && 2 * kBxLdsSlot <= kBxLdsTarget,
               "the CU's slot grid: six slots of whole LDS granules within 160 KB, a forward request within its target");
 
+// A float sum of integer terms whose every partial sum, in any order, is an
+// integer of magnitude <= kExact is exact: its integer value (psn_lk_device.h).
+constexpr int kExact = 1 << 24;
 constexpr int kStEPTMax = 4;  // window pixels per thread held in registers by the single-tile kernel
+// The single-tile kernel's err sum has no ordered-float path: a window value is a
+// bilinear sum of bytes with weights summing to 2^14, descaled by 9 bits, so
+// |J - I| <= 255 * 32, and the planner gives the kernel at most 256 * kStEPTMax pixels.
+constexpr long kStErrSumMax = 256L * kStEPTMax * 255 * 32;
+static_assert(kStErrSumMax <= kExact, "kStEPTMax: lk_kernel_st's err sum could pass 2^24 and needs an ordered float sum");
 constexpr int kStMaxLds = 150 * 1024;
 
 // Launchers, one translation unit per kernel family.

@@ -368,6 +368,177 @@ __device__ __forceinline__ void st_level_table(float *lv, unsigned a11, int s12,
     lv[5] = S.ok ? 1.f : 0.f;
 }
 
+// ---- the phases of lk_kernel_st, each written once. The helpers take scalar
+// fields and pointers, never the launch arguments or a query whole (an inlined
+// function reading those through a parameter keeps a private copy in scratch:
+// psn_lk_bx_body.inc). ----
+
+// Scharr plane (Ix, Iy as short2, (h + 1) x DW) of one level's I patch P (row
+// stride RS, top-left at image pixel (ipx - 1, ipy - 1)); zero where the centre
+// pixel is outside the cols x rows image. Thread t of a group of NT.
+template <int NT>
+__device__ __forceinline__ void scharr_plane(short2 *Dg, const uint8_t *P, int RS, int DW, int h, unsigned dv_dw, int ipx,
+                                             int ipy, int cols, int rows, int t) {
+    Walk wk;
+    wk.init_m(t, NT, DW, dv_dw);
+    for (int idx = t; idx < (h + 1) * DW; idx += NT, wk.step()) {
+        const int gy = ipy + wk.y, gx = ipx + wk.x;
+        short2 d = make_short2(0, 0);
+        if ((unsigned)gy < (unsigned)rows && (unsigned)gx < (unsigned)cols) {
+            const uint8_t *p = P + wk.y * RS + wk.x;
+            const int a0 = p[0], a1 = p[1], a2 = p[2];
+            const int b0 = p[RS], b2 = p[RS + 2];
+            const int c0 = p[2 * RS], c1 = p[2 * RS + 1], c2 = p[2 * RS + 2];
+            d.x = (short)(3 * (a2 + c2) + 10 * b2 - 3 * (a0 + c0) - 10 * b0);
+            d.y = (short)(3 * ((c0 - a0) + (c2 - a2)) + 10 * (c1 - a1));
+        }
+        Dg[idx] = d;
+    }
+}
+
+// One window pixel of the A phase: the bilinear window value (5 fractional bits)
+// and gradients from the patch at p and the Scharr plane at d, {Iw, Ix | Iy << 16}
+// into *iw when the pixel is valid, the three tensor products into the chain planes
+// PA (plane stride GP) at pos, and the thread's integer sums. An idle lane
+// (!valid) carries zero gradients and writes its zero products into a pad slot.
+__device__ __forceinline__ void a_pixel(const uint8_t *p, int RS, const short2 *d, int DW, const IGeo &gg, bool valid,
+                                        int2 *iw_out, float *PA, int GP, int pos, unsigned &s11, int &s12, unsigned &s22) {
+    const int iw = PSN_DESCALE(__mul24((int)p[0], gg.w00) + __mul24((int)p[1], gg.w01) +
+                                   __mul24((int)p[RS], gg.w10) + __mul24((int)p[RS + 1], gg.w11), 9);
+    const short2 d00 = d[0], d01 = d[1], d10 = d[DW], d11 = d[DW + 1];
+    int ix = PSN_DESCALE(__mul24((int)d00.x, gg.w00) + __mul24((int)d01.x, gg.w01) +
+                             __mul24((int)d10.x, gg.w10) + __mul24((int)d11.x, gg.w11), 14);
+    int iy = PSN_DESCALE(__mul24((int)d00.y, gg.w00) + __mul24((int)d01.y, gg.w01) +
+                             __mul24((int)d10.y, gg.w10) + __mul24((int)d11.y, gg.w11), 14);
+    if (valid) *iw_out = make_int2(iw, (ix & 0xffff) | (iy << 16));
+    ix = valid ? ix : 0;
+    iy = valid ? iy : 0;
+    const int xx2 = __mul24(ix, ix), xy = __mul24(ix, iy), yy2 = __mul24(iy, iy);
+    PA[pos] = (float)xx2;
+    PA[GP + pos] = (float)xy;
+    PA[2 * GP + pos] = (float)yy2;
+    s11 += (unsigned)xx2;  // |Ix|, |Iy| <= 4080: up to 16 pixels per thread stay < 2^30
+    s12 += xy;
+    s22 += (unsigned)yy2;
+}
+
+// Chain ch (0-3 the SSE2 lanes, 4 the tail) of A sum s (0: A11, 1: A12, 2: A22)
+// of the level whose three planes start at PA: its ordered float sum, or 0 when
+// the sum is exact as an integer and st_level_table will not use the chains.
+// Per-sum exactness: A11 (terms >= 0) is exact when s11 <= 2^24, A22 when
+// s22 <= 2^24, A12 when sum|xy| <= (s11 + s22) / 2 <= 2^24.
+__device__ __forceinline__ float a_chain(const float *PA, const ChainGeo &GA, int s, int ch, unsigned a11, unsigned a22) {
+    const unsigned bound = s == 0 ? a11 : s == 2 ? a22 : (a11 + a22) >> 1;
+    float acc = 0.f;
+    if (bound > (unsigned)kExact) {
+        const int base = s * GA.P + (ch < 4 ? ch * GA.S : 4 * GA.S);
+        acc = chain_sum16(PA + base, (ch < 4 ? GA.S : GA.T) >> 4);
+    }
+    return acc;
+}
+
+// The 10 ordered b chains of the planes at pb (lanes 0-9 of the calling wave sum
+// one chain each), combined in the SSE2 build's order. Uniform results.
+__device__ __forceinline__ void b_chains(const float *pb, const ChainGeo &GB, bool sse, int lane, float &b1, float &b2) {
+    float acc = 0.f;
+    if (lane < 10) {
+        const int ch = lane % 5, s = lane / 5;
+        const int base = s * GB.P + (ch < 4 ? ch * GB.S : 4 * GB.S);
+        const int nb = (ch < 4 ? GB.S : GB.T) >> 4;
+        acc = chain_sum16(pb + base, nb);
+    }
+    combine_b10([&](int i) { return readlane_f(acc, i); }, sse, b1, b2);
+}
+
+// The guess a level starts from: at the coarsest level the initial flow (or the
+// previous point) scaled to it, below it twice the level above's result.
+struct Guess {
+    float x, y;
+};
+__device__ __forceinline__ Guess level_guess(int level, int maxL, int flags, float px0, float py0, float NPx, float NPy) {
+    Guess gs;
+    const float scale = ldexpf(1.f, -level);
+    if (level == maxL) {
+        if (flags & PSN_LK_USE_INITIAL_FLOW) {
+            gs.x = __fmul_rn(NPx, scale);
+            gs.y = __fmul_rn(NPy, scale);
+        } else {
+            gs.x = __fmul_rn(px0, scale);
+            gs.y = __fmul_rn(py0, scale);
+        }
+    } else {
+        gs.x = __fmul_rn(NPx, 2.f);
+        gs.y = __fmul_rn(NPy, 2.f);
+    }
+    return gs;
+}
+
+// Start of a level: NP becomes the level's guess; the level's solver row lv; run
+// = the I window is inside the image and the system is solvable; status and err
+// of a level that does not run (they count at level 0 only); the J window's
+// start (nx, ny) = NP - halfWin.
+struct LevelStart {
+    float nx, ny;
+    const float *lv;
+    bool run;
+};
+__device__ __forceinline__ LevelStart level_start(int level, int maxL, int flags, float px0, float py0, float hwx,
+                                                  float hwy, int w, int h, int cols, int rows, const float *LV,
+                                                  float &NPx, float &NPy, int &status, float &errv) {
+    LevelStart ls;
+    const Guess gs = level_guess(level, maxL, flags, px0, py0, NPx, NPy);
+    NPx = gs.x;
+    NPy = gs.y;
+    const IGeo gg = i_geo(px0, py0, hwx, hwy, level, w, h, cols, rows);
+    ls.lv = LV + level * kStLvFloats;
+    ls.run = gg.valid && ls.lv[5] != 0.f;
+    if (!gg.valid) {
+        if (level == 0) {
+            status = 0;
+            errv = 0.f;
+        }
+    } else {
+        if (flags & PSN_LK_GET_MIN_EIGENVALS) errv = ls.lv[4];
+        if (!ls.run && level == 0) status = 0;
+    }
+    ls.nx = __fsub_rn(gs.x, hwx);
+    ls.ny = __fsub_rn(gs.y, hwy);
+    return ls;
+}
+
+// Origin of the J region staged for a window whose integer start is (ix, iy):
+// kStJMargin pixels up and left, the column aligned down to 4 (JPStage).
+// uniform: through readfirstlane, for an origin every lane computed alike.
+struct JOrigin {
+    int x0, y0;
+};
+__device__ __forceinline__ JOrigin jr_origin(int ix, int iy, bool uniform) {
+    JOrigin o;
+    o.x0 = (ix - kStJMargin) & ~3;
+    o.y0 = iy - kStJMargin;
+    if (uniform) {
+        o.x0 = __builtin_amdgcn_readfirstlane(o.x0);
+        o.y0 = __builtin_amdgcn_readfirstlane(o.y0);
+    }
+    return o;
+}
+
+// Synchronous restage of the J region at origin o into dst by the threads of the
+// walk pair (wi interior, wb border). cs > 0: column-major with stride cs (the
+// one-wave layout), 0: row-major. wave_local: one wave restages a region that it
+// alone reads, between its own reads of the old contents and of the new -- LDS
+// executes a wave's accesses in order, the waits keep the compiler from moving
+// them across the copy; without it the caller's barriers order the copy.
+template <int NT>
+__device__ __forceinline__ void jr_restage(uint32_t *dst, const LevelDev &J, JOrigin o, int JRW, int JRH, int cs,
+                                           const JWalk &wi, const JWalk &wb, bool wave_local) {
+    JPStage<NT> cp;
+    cp.cs = cs;
+    if (wave_local) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    cp.copy(dst, J, o.y0, o.x0, JRW, JRH, wi, wb);
+    if (wave_local) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
 // Diagnostic stamps of the single-tile kernel (PSN_LK_STAMPS): 60 start, 50
 // prologue landed, 51 Scharr of all levels, 52 A products + reduction, 53
 // solver table; per level L*10+0 start, +1 J staged, +2 window loaded, +7
@@ -406,14 +577,14 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
     int *RI = (int *)(smem + lay.ri);
     float *LV = (float *)(smem + lay.lv);
     uint32_t *JP = (uint32_t *)(smem + lay.jp);
-    float *R = (float *)(smem + lay.r);    // b chain planes / err row (iterations)
+    float *R = (float *)(smem + lay.r);    // b chain planes (iterations)
     float *RA = (float *)(smem + lay.ra);  // A-phase chain planes (prologue; == R outside the one-wave layout)
     const ChainGeo GA = chain_geo_A(w, h, sse), GB = chain_geo_B(w, h, sse);
 
     // ---- per-thread window pixels (fixed for the whole kernel). Idle lanes
     // (pixel index >= w*h) read pixel 0, carry zero gradients and write their
     // zero products into a pad slot of the chain planes: branch-free loops.
-    int ofsJ[EPT], ofsP[EPT], ofsD[EPT], posA_[EPT], posB_[EPT], ofsE[EPT], pix[EPT];
+    int ofsJ[EPT], ofsP[EPT], ofsD[EPT], posA_[EPT], posB_[EPT], pix[EPT];
     bool ev[EPT];
 #pragma unroll
     for (int k = 0; k < EPT; k++) {
@@ -427,7 +598,6 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
         ofsD[k] = y * DW + x;
         posA_[k] = ev[k] ? posA(GA, y, x) : 4 * GA.S + GA.lenT;
         posB_[k] = ev[k] ? posB(GB, y, x) : 4 * GB.S + GB.lenT;
-        ofsE[k] = ev[k] ? idx : round16i(wh);  // err plane (row-major): idle lanes write past the end
     }
 
     // the point's waves outrank fused pyramid-tile waves sharing their SIMDs
@@ -470,16 +640,14 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
         tbl_put(TBL, ts, tl, L);
     }
     LK_STAMP(63);
-    JPStage<NT> pf;  // prefetched J region of level pf_level at (pf_y0, pf_x0)
-    int pf_level, pf_x0, pf_y0;
+    JPStage<NT> pf;  // prefetched J region of level pf_level at origin pfo
+    int pf_level = maxL;
+    JOrigin pfo;
     {
-        const float sc = ldexpf(1.f, -maxL);
-        const float nx0 = (flags & PSN_LK_USE_INITIAL_FLOW) ? __fmul_rn(NPx, sc) : __fmul_rn(px0, sc);
-        const float ny0 = (flags & PSN_LK_USE_INITIAL_FLOW) ? __fmul_rn(NPy, sc) : __fmul_rn(py0, sc);
-        pf_x0 = (cv_floor(__fsub_rn(nx0, hwx)) - kStJMargin) & ~3;
-        pf_y0 = cv_floor(__fsub_rn(ny0, hwy)) - kStJMargin;
-        pf_level = maxL;
-        pf.load(ring_level_u(A.ring, Q.next_slot, maxL), pf_y0, pf_x0, JRW, JRH, wk_int, wk_bord);
+        // the coarsest level's start as level_start will compute it
+        const Guess gs = level_guess(maxL, maxL, flags, px0, py0, NPx, NPy);
+        pfo = jr_origin(cv_floor(__fsub_rn(gs.x, hwx)), cv_floor(__fsub_rn(gs.y, hwy)), false);
+        pf.load(ring_level_u(A.ring, Q.next_slot, maxL), pfo.y0, pfo.x0, JRW, JRH, wk_int, wk_bord);
     }
     LK_STAMP(59);
     dma_wait();
@@ -499,21 +667,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
         if (!gg.valid) continue;
         const uint8_t *P = smem + lay.pim + l * lay.pim_stride + ((gg.ipx - 1) & 3);
         short2 *Dg = (short2 *)(smem + lay.dg + l * lay.dg_stride);
-        Walk wk;
-        wk.init_m(tid, NT, DW, Q.dv_dw);
-        for (int idx = tid; idx < (h + 1) * DW; idx += NT, wk.step()) {
-            const int gy = gg.ipy + wk.y, gx = gg.ipx + wk.x;
-            short2 d = make_short2(0, 0);
-            if ((unsigned)gy < (unsigned)I.h && (unsigned)gx < (unsigned)I.w) {
-                const uint8_t *p = P + wk.y * RS + wk.x;
-                const int a0 = p[0], a1 = p[1], a2 = p[2];
-                const int b0 = p[RS], b2 = p[RS + 2];
-                const int c0 = p[2 * RS], c1 = p[2 * RS + 1], c2 = p[2 * RS + 2];
-                d.x = (short)(3 * (a2 + c2) + 10 * b2 - 3 * (a0 + c0) - 10 * b0);
-                d.y = (short)(3 * ((c0 - a0) + (c2 - a2)) + 10 * (c1 - a1));
-            }
-            Dg[idx] = d;
-        }
+        scharr_plane<NT>(Dg, P, RS, DW, h, Q.dv_dw, gg.ipx, gg.ipy, I.w, I.h, tid);
     }
     __syncthreads();
     LK_STAMP(51);
@@ -523,9 +677,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
         if (l < lo) continue;
         const LevelDev I = ring_level(A.ring, Q.prev_slot, l);
         const IGeo gg = i_geo(px0, py0, hwx, hwy, l, w, h, I.w, I.h);
-        // Per-sum exactness: A11 (terms >= 0) is exact when s11 <= 2^24, A22 when
-        // s22 <= 2^24, A12 when sum|xy| <= (s11 + s22) / 2 <= 2^24; s11 and s22
-        // are reduced saturating, s12 wrapping
+        // s11 and s22 are reduced saturating, s12 wrapping (a_chain: the exactness bounds)
         unsigned s11 = 0, s22 = 0;
         int s12 = 0;
         if (gg.valid) {
@@ -534,27 +686,8 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
             int2 *IW = (int2 *)(smem + lay.iw + l * lay.iw_stride);
             float *PA = RA + l * 3 * GA.P;
 #pragma unroll
-            for (int k = 0; k < EPT; k++) {
-                const uint8_t *p = P + ofsP[k];
-                const int iw = PSN_DESCALE(__mul24((int)p[0], gg.w00) + __mul24((int)p[1], gg.w01) +
-                                               __mul24((int)p[RS], gg.w10) + __mul24((int)p[RS + 1], gg.w11), 9);
-                const short2 *d = Dg + ofsD[k];
-                const short2 d00 = d[0], d01 = d[1], d10 = d[DW], d11 = d[DW + 1];
-                int ix = PSN_DESCALE(__mul24((int)d00.x, gg.w00) + __mul24((int)d01.x, gg.w01) +
-                                         __mul24((int)d10.x, gg.w10) + __mul24((int)d11.x, gg.w11), 14);
-                int iy = PSN_DESCALE(__mul24((int)d00.y, gg.w00) + __mul24((int)d01.y, gg.w01) +
-                                         __mul24((int)d10.y, gg.w10) + __mul24((int)d11.y, gg.w11), 14);
-                if (ev[k]) IW[pix[k]] = make_int2(iw, (ix & 0xffff) | (iy << 16));
-                ix = ev[k] ? ix : 0;
-                iy = ev[k] ? iy : 0;
-                const int xx2 = __mul24(ix, ix), xy = __mul24(ix, iy), yy2 = __mul24(iy, iy);
-                PA[posA_[k]] = (float)xx2;
-                PA[GA.P + posA_[k]] = (float)xy;
-                PA[2 * GA.P + posA_[k]] = (float)yy2;
-                s11 += (unsigned)xx2;  // per thread <= 4 * 4080^2 < 2^30
-                s12 += xy;
-                s22 += (unsigned)yy2;
-            }
+            for (int k = 0; k < EPT; k++)
+                a_pixel(P + ofsP[k], RS, Dg + ofsD[k], DW, gg, ev[k], IW + pix[k], PA, GA.P, posA_[k], s11, s12, s22);
         }
         s11 = wave_sum_sat(s11);
         s12 = wave_sum(s12);
@@ -583,14 +716,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                     a22 = sat_add(a22, (unsigned)RI[kStRiA + l * 32 + 16 + ww]);
                 }
                 const int s = r / 5, ch = r - 5 * (r / 5);
-                const unsigned bound = s == 0 ? a11 : s == 2 ? a22 : (a11 + a22) >> 1;
-                float acc = 0.f;
-                if (bound > (unsigned)kExact) {
-                    const int base = (l * 3 + s) * GA.P + (ch < 4 ? ch * GA.S : 4 * GA.S);
-                    const int nb = (ch < 4 ? GA.S : GA.T) >> 4;
-                    acc = chain_sum16(RA + base, nb);
-                }
-                CH[q] = acc;
+                CH[q] = a_chain(RA + l * 3 * GA.P, GA, s, ch, a11, a22);
             }
         }
         // CH written by other lanes of this wave: LDS executes a wave's accesses in
@@ -621,7 +747,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
     float errv = 0.f;
     // accumulated iteration phases (slots 40..47), ordered stamps
     PSN_STAMPS_ONLY(unsigned long long acc_ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_ph = 0;)
-    int jr_x0 = 0, jr_y0 = 0;
+    JOrigin jr = {0, 0};  // origin of the staged J region
 
     if constexpr (E > 0) {
         // ---- one-wave iterations: wave 0 runs the LK iterations of every level
@@ -677,67 +803,26 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
             dma_wait();
             const uint8_t *P = pim + ((gg.ipx - 1) & 3);
             short2 *Dg = (short2 *)(smem + lay.dg + l * lay.dg_stride);
-            {
-                Walk wk;
-                wk.init_m(lane, 64, DW, Q.dv_dw);
-                for (int idx = lane; idx < (h + 1) * DW; idx += 64, wk.step()) {
-                    const int gy = gg.ipy + wk.y, gx = gg.ipx + wk.x;
-                    short2 d = make_short2(0, 0);
-                    if ((unsigned)gy < (unsigned)I.h && (unsigned)gx < (unsigned)I.w) {
-                        const uint8_t *p = P + wk.y * RS + wk.x;
-                        const int a0 = p[0], a1 = p[1], a2 = p[2];
-                        const int b0 = p[RS], b2 = p[RS + 2];
-                        const int c0 = p[2 * RS], c1 = p[2 * RS + 1], c2 = p[2 * RS + 2];
-                        d.x = (short)(3 * (a2 + c2) + 10 * b2 - 3 * (a0 + c0) - 10 * b0);
-                        d.y = (short)(3 * ((c0 - a0) + (c2 - a2)) + 10 * (c1 - a1));
-                    }
-                    Dg[idx] = d;
-                }
-            }
+            scharr_plane<64>(Dg, P, RS, DW, h, Q.dv_dw, gg.ipx, gg.ipy, I.w, I.h, lane);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             int2 *IW = (int2 *)(smem + lay.iw + l * lay.iw_stride);
             float *PA = RA + l * 3 * GA.P;
-            unsigned s11 = 0, s22 = 0;  // per lane <= 16 * 4080^2 < 2^30
+            unsigned s11 = 0, s22 = 0;
             int s12 = 0;
             for (int i0 = 0; i0 < wh; i0 += 64) {
                 const int idx = i0 + lane;
                 const bool v = idx < wh;
                 const int i = v ? idx : 0;
                 const int y = qdiv(i, Q.dv_w), x = i - y * w;
-                const uint8_t *p = P + (y + 1) * RS + x + 1;
-                const int iw = PSN_DESCALE(__mul24((int)p[0], gg.w00) + __mul24((int)p[1], gg.w01) +
-                                               __mul24((int)p[RS], gg.w10) + __mul24((int)p[RS + 1], gg.w11), 9);
-                const short2 *d = Dg + y * DW + x;
-                const short2 d00 = d[0], d01 = d[1], d10 = d[DW], d11 = d[DW + 1];
-                int ix = PSN_DESCALE(__mul24((int)d00.x, gg.w00) + __mul24((int)d01.x, gg.w01) +
-                                         __mul24((int)d10.x, gg.w10) + __mul24((int)d11.x, gg.w11), 14);
-                int iy = PSN_DESCALE(__mul24((int)d00.y, gg.w00) + __mul24((int)d01.y, gg.w01) +
-                                         __mul24((int)d10.y, gg.w10) + __mul24((int)d11.y, gg.w11), 14);
-                if (v) IW[i] = make_int2(iw, (ix & 0xffff) | (iy << 16));
-                ix = v ? ix : 0;
-                iy = v ? iy : 0;
-                const int xx2 = __mul24(ix, ix), xy = __mul24(ix, iy), yy2 = __mul24(iy, iy);
-                const int pos = v ? posA(GA, y, x) : 4 * GA.S + GA.lenT;
-                PA[pos] = (float)xx2;
-                PA[GA.P + pos] = (float)xy;
-                PA[2 * GA.P + pos] = (float)yy2;
-                s11 += (unsigned)xx2;
-                s12 += xy;
-                s22 += (unsigned)yy2;
+                a_pixel(P + (y + 1) * RS + x + 1, RS, Dg + y * DW + x, DW, gg, v, IW + i, PA, GA.P,
+                        v ? posA(GA, y, x) : 4 * GA.S + GA.lenT, s11, s12, s22);
             }
             s11 = wave_sum_sat(s11);
             s12 = wave_sum(s12);
             s22 = wave_sum_sat(s22);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             float acc = 0.f;
-            if (lane < 15) {
-                const int sm = lane / 5, ch = lane - 5 * sm;
-                const unsigned bound = sm == 0 ? s11 : sm == 2 ? s22 : (s11 + s22) >> 1;
-                if (bound > (unsigned)kExact) {
-                    const int base = sm * GA.P + (ch < 4 ? ch * GA.S : 4 * GA.S);
-                    acc = chain_sum16(PA + base, (ch < 4 ? GA.S : GA.T) >> 4);
-                }
-            }
+            if (lane < 15) acc = a_chain(PA, GA, lane / 5, lane - 5 * (lane / 5), s11, s22);
             float c[15];
 #pragma unroll
             for (int k = 0; k < 15; k++) c[k] = readlane_f(acc, k);
@@ -754,63 +839,34 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
             const LevelDev I = tbl_get(TBL, 0, level);
             const LevelDev J = tbl_get(TBL, 1, level);
             const int cols = I.w, rows = I.h;
-            const float scale = ldexpf(1.f, -level);
-            float nx, ny;
-            if (level == maxL) {
-                if (flags & PSN_LK_USE_INITIAL_FLOW) {
-                    nx = __fmul_rn(NPx, scale);
-                    ny = __fmul_rn(NPy, scale);
-                } else {
-                    nx = __fmul_rn(px0, scale);
-                    ny = __fmul_rn(py0, scale);
-                }
-            } else {
-                nx = __fmul_rn(NPx, 2.f);
-                ny = __fmul_rn(NPy, 2.f);
-            }
-            NPx = nx;
-            NPy = ny;
-            const IGeo gg = i_geo(px0, py0, hwx, hwy, level, w, h, cols, rows);
-            const float *lv = LV + level * kStLvFloats;
-            const bool run = gg.valid && lv[5] != 0.f;
-            if (!gg.valid) {
-                if (level == 0) {
-                    status = 0;
-                    errv = 0.f;
-                }
-            } else {
-                if (flags & PSN_LK_GET_MIN_EIGENVALS) errv = lv[4];
-                if (!run && level == 0) status = 0;
-            }
-            nx = __fsub_rn(nx, hwx);
-            ny = __fsub_rn(ny, hwy);
+            const LevelStart ls =
+                level_start(level, maxL, flags, px0, py0, hwx, hwy, w, h, cols, rows, LV, NPx, NPy, status, errv);
+            const float *lv = ls.lv;
+            const bool run = ls.run;
+            float nx = ls.nx, ny = ls.ny;
             uint32_t *const JC = buf ? JPB1 : JPB0;
             if (run) {
                 const int inx0 = __builtin_amdgcn_readfirstlane(cv_floor(nx));
                 const int iny0 = __builtin_amdgcn_readfirstlane(cv_floor(ny));
-                if (pf_level == level && jr_covers(inx0, iny0, w, h, pf_x0, pf_y0, JRW, JRH)) {
+                if (pf_level == level && jr_covers(inx0, iny0, w, h, pfo.x0, pfo.y0, JRW, JRH)) {
                     if (pf_regs) {
                         LK_STAMP(55);
                         pf.store(JC);
                         LK_STAMP(56);
                     }
-                    jr_x0 = pf_x0;
-                    jr_y0 = pf_y0;
+                    jr = pfo;
                 } else {
-                    JPStage<NT> cp;
-                    cp.cs = JRHc;
-                    jr_x0 = (inx0 - kStJMargin) & ~3;
-                    jr_y0 = iny0 - kStJMargin;
-                    cp.copy(JC, J, jr_y0, jr_x0, JRW, JRH, wk_int, wk_bord);
+                    jr = jr_origin(inx0, iny0, false);
+                    jr_restage<NT>(JC, J, jr, JRW, JRH, JRHc, wk_int, wk_bord, false);
                 }
             }
             pf_regs = false;
             __syncthreads();  // JC complete; every wave is past the previous level
             LK_STAMP(level * 10 + 1);
-            // next level's region at its predicted start (2 x this start)
+            // next level's region where this level's start predicts it
             pf_level = level > 0 ? level - 1 : -1;
-            pf_x0 = __builtin_amdgcn_readfirstlane((cv_floor(__fsub_rn(__fmul_rn(NPx, 2.f), hwx)) - kStJMargin) & ~3);
-            pf_y0 = __builtin_amdgcn_readfirstlane(cv_floor(__fsub_rn(__fmul_rn(NPy, 2.f), hwy)) - kStJMargin);
+            const Guess gn = level_guess(level - 1, maxL, flags, px0, py0, NPx, NPy);
+            pfo = jr_origin(cv_floor(__fsub_rn(gn.x, hwx)), cv_floor(__fsub_rn(gn.y, hwy)), true);
 
             if (wid != 0) {
                 if (ovl && level == maxL) {  // the finer levels' A phase: wave k takes levels maxL - k, maxL - k - 3, ...
@@ -818,12 +874,9 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                     // wave k's A phase done: slot 59 - 10 k
                     PSN_STAMP(A.stamps, lane == 0 && wid < 4, (size_t)blockIdx.x * 64 + 59 - 10 * wid);
                 }
-                if (level > 0) {
-                    JPStage<NT> cp;
-                    cp.cs = JRHc;
-                    cp.copy(buf ? JPB0 : JPB1, tbl_get(TBL, 1, level - 1), pf_y0, pf_x0, JRW, JRH,
-                            wkh_int, wkh_bord);
-                }
+                if (level > 0)
+                    jr_restage<NT>(buf ? JPB0 : JPB1, tbl_get(TBL, 1, level - 1), pfo, JRW, JRH, JRHc, wkh_int, wkh_bord,
+                                   false);
             } else if (run) {
                 const float A11 = lv[0], A12 = lv[1], A22 = lv[2], D = lv[3];
                 // the lane's window rows, two rows per dword (int16 halves): I, Ix,
@@ -894,7 +947,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                     const unsigned W0 = pack_w(iw00, iw01), W1 = pack_w(iw10, iw11);
                     // speculative: the offsets are clamped into the region, the
                     // bounds / region tests below decide whether the sums count
-                    const int ox = min(max(inx - jr_x0, 0), JRW - w - 1), oy = min(max(iny - jr_y0, 0), JRH - h - 1);
+                    const int ox = min(max(inx - jr.x0, 0), JRW - w - 1), oy = min(max(iny - jr.y0, 0), JRH - h - 1);
                     int s1, s2;
                     unsigned a, a2;
                     products(ox, oy, W0, W1, s1, s2, a, a2);
@@ -907,16 +960,11 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                         if (level == 0) status = 0;
                         break;
                     }
-                    if (!(jr_covers(sinx, siny, w, h, jr_x0, jr_y0, JRW, JRH))) {
+                    if (!(jr_covers(sinx, siny, w, h, jr.x0, jr.y0, JRW, JRH))) {
                         // restage by this wave alone (the other waves never read JC)
-                        JPStage<NT> cp;
-                        cp.cs = JRHc;
-                        jr_x0 = __builtin_amdgcn_readfirstlane((sinx - kStJMargin) & ~3);
-                        jr_y0 = __builtin_amdgcn_readfirstlane(siny - kStJMargin);
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        cp.copy(JC, J, jr_y0, jr_x0, JRW, JRH, wk0_int, wk0_bord);
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        products(sinx - jr_x0, siny - jr_y0, W0, W1, s1, s2, a, a2);
+                        jr = jr_origin(sinx, siny, true);
+                        jr_restage<NT>(JC, J, jr, JRW, JRH, JRHc, wk0_int, wk0_bord, true);
+                        products(sinx - jr.x0, siny - jr.y0, W0, W1, s1, s2, a, a2);
                         PSN_PH_COUNT(acc_ph, 5);
                     }
                     PSN_PH_MARK(acc_ph, t_ph, 0);
@@ -971,14 +1019,7 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                                 }
                             }
                             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                            float acc = 0.f;
-                            if (lane < 10) {
-                                const int ch = lane % 5, s = lane / 5;
-                                const int base = s * GB.P + (ch < 4 ? ch * GB.S : 4 * GB.S);
-                                const int nb = (ch < 4 ? GB.S : GB.T) >> 4;
-                                acc = chain_sum16(R + base, nb);
-                            }
-                            combine_b10([&](int i) { return readlane_f(acc, i); }, sse, b1, b2);
+                            b_chains(R, GB, sse, lane, b1, b2);
                             PSN_PH_COUNT(acc_ph, 4);
                         }
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // CSX / R reads done before the next writes
@@ -1001,42 +1042,23 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
                     } else if ((flags & PSN_LK_ERR_STATUS_ONLY) == 0) {  // (else the re-check was all: err[] = 0)
                         int iw00, iw01, iw10, iw11;
                         bilin_weights(__fsub_rn(qx, (float)iqx), __fsub_rn(qy, (float)iqy), iw00, iw01, iw10, iw11);
-                        if (!(jr_covers(iqx, iqy, w, h, jr_x0, jr_y0, JRW, JRH))) {
-                            JPStage<NT> cp;
-                            cp.cs = JRHc;
-                            jr_x0 = (iqx - kStJMargin) & ~3;
-                            jr_y0 = iqy - kStJMargin;
-                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                            cp.copy(JC, J, jr_y0, jr_x0, JRW, JRH, wk0_int, wk0_bord);
-                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                        if (!(jr_covers(iqx, iqy, w, h, jr.x0, jr.y0, JRW, JRH))) {
+                            jr = jr_origin(iqx, iqy, false);
+                            jr_restage<NT>(JC, J, jr, JRW, JRH, JRHc, wk0_int, wk0_bord, true);
                         }
                         const unsigned W0 = pack_w(iw00, iw01), W1 = pack_w(iw10, iw11);
-                        const uint32_t *jb = JC + (iqx - jr_x0) * JRHc + (iqy - jr_y0) + lane_off;
+                        const uint32_t *jb = JC + (iqx - jr.x0) * JRHc + (iqy - jr.y0) + lane_off;
                         unsigned ea = 0;
-                        int ad[E];
 #pragma unroll
                         for (int k = 0; k < E; k++) {
                             const int jv = sdot2(jb[k + 1], W1, sdot2(jb[k], W0, 1 << 8)) >> 9;
                             const int y = oy0 + k;
-                            ad[k] = (lane_on && k < RG && y < h) ? abs(jv - Iw_[k]) : 0;
-                            ea += (unsigned)ad[k];
+                            ea += (unsigned)((lane_on && k < RG && y < h) ? abs(jv - Iw_[k]) : 0);
                         }
                         ea = (unsigned)__builtin_amdgcn_readlane(wave_scan((int)ea), 63);
-                        float errval;
-                        if (ea <= (unsigned)kExact) {
-                            errval = (float)ea;  // every partial sum of errval += |diff| is an exact integer
-                        } else {  // row-major order, one lane
-#pragma unroll
-                            for (int k = 0; k < E; k++) {
-                                const int y = oy0 + k;
-                                if (lane_on && k < RG && y < h) R[y * w + colx] = (float)ad[k];
-                            }
-                            for (int k = wh + lane; k < round16i(wh); k += 64) R[k] = 0.f;
-                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                            float acc = 0.f;
-                            if (lane == 0) acc = chain_sum16(R, round16i(wh) >> 4);
-                            errval = readlane_f(acc, 0);
-                        }
+                        // ea <= kStErrSumMax <= kExact (psn_lk_kernels.h): every partial sum of
+                        // errval += |diff|, in any order, is an exact integer
+                        const float errval = (float)ea;
                         errv = lk_err(errval, wh);
                     }
                 }
@@ -1051,193 +1073,151 @@ __global__ __launch_bounds__(NT, OCC) void lk_kernel_st(LkLaunchArgs A) {
             buf ^= 1;
         }
     } else {
-    for (int level = maxL; level >= 0; level--) {
-        LK_STAMP(level * 10 + 0);
-        const LevelDev I = tbl_get(TBL, 0, level);
-        const LevelDev J = tbl_get(TBL, 1, level);
-        const int cols = I.w, rows = I.h;
-        const float scale = ldexpf(1.f, -level);
-        float nx, ny;
-        if (level == maxL) {
-            if (flags & PSN_LK_USE_INITIAL_FLOW) {
-                nx = __fmul_rn(NPx, scale);
-                ny = __fmul_rn(NPy, scale);
-            } else {
-                nx = __fmul_rn(px0, scale);
-                ny = __fmul_rn(py0, scale);
-            }
-        } else {
-            nx = __fmul_rn(NPx, 2.f);
-            ny = __fmul_rn(NPy, 2.f);
-        }
-        NPx = nx;
-        NPy = ny;
-        const IGeo gg = i_geo(px0, py0, hwx, hwy, level, w, h, cols, rows);
-        const float *lv = LV + level * kStLvFloats;
-        const bool run = gg.valid && lv[5] != 0.f;
-        if (!gg.valid) {
-            if (level == 0) {
-                status = 0;
-                errv = 0.f;
-            }
-        } else {
-            if (flags & PSN_LK_GET_MIN_EIGENVALS) errv = lv[4];
-            if (!run && level == 0) status = 0;
-        }
-        nx = __fsub_rn(nx, hwx);
-        ny = __fsub_rn(ny, hwy);
-        if (run) {
-            // this level's J region: the prefetched registers if they cover the start
-            const int inx0 = cv_floor(nx), iny0 = cv_floor(ny);
-            if (pf_level == level && jr_covers(inx0, iny0, w, h, pf_x0, pf_y0, JRW, JRH)) {
-                pf.store(JP);
-                jr_x0 = pf_x0;
-                jr_y0 = pf_y0;
-            } else {
-                JPStage<NT> cp;
-                jr_x0 = (inx0 - kStJMargin) & ~3;
-                jr_y0 = iny0 - kStJMargin;
-                cp.copy(JP, J, jr_y0, jr_x0, JRW, JRH, wk_int, wk_bord);
-            }
-        }
-        pf_level = -1;
-        if (level > 0) {  // prefetch the next level's region at its predicted start (2 x this start)
-            pf_x0 = (cv_floor(__fsub_rn(__fmul_rn(NPx, 2.f), hwx)) - kStJMargin) & ~3;
-            pf_y0 = cv_floor(__fsub_rn(__fmul_rn(NPy, 2.f), hwy)) - kStJMargin;
-            pf_level = level - 1;
-            pf.load(tbl_get(TBL, 1, level - 1), pf_y0, pf_x0, JRW, JRH, wk_int, wk_bord);
-        }
-        if (!run) continue;
-        __syncthreads();  // JP published (every wave finished the previous level's reads)
-        LK_STAMP(level * 10 + 1);
-
-        const float A11 = lv[0], A12 = lv[1], A22 = lv[2], D = lv[3];
-        int Iw_[EPT], Ix_[EPT], Iy_[EPT];
-        unsigned Sxy[EPT];
-        {
-            const int2 *IW = (const int2 *)(smem + lay.iw + level * lay.iw_stride);
-#pragma unroll
-            for (int k = 0; k < EPT; k++) {
-                const int2 t = IW[pix[k]];
-                Iw_[k] = t.x;
-                Ix_[k] = ev[k] ? (int)(short)(t.y & 0xffff) : 0;
-                Iy_[k] = ev[k] ? (t.y >> 16) : 0;
-                Sxy[k] = (unsigned)(abs(Ix_[k]) + abs(Iy_[k]));
-            }
-        }
-        LK_STAMP(level * 10 + 2);
-        float pdx = 0.f, pdy = 0.f;
-        int jdone = 0;
-
-        for (int j = 0; j < Q.max_count; j++) {
-            jdone = j + 1;
-            PSN_CLK_ORDERED(t_ph);
-            const int inx = cv_floor(nx), iny = cv_floor(ny);
-            if (win_outside(inx, iny, w, h, cols, rows)) {
-                if (level == 0) status = 0;
-                break;
-            }
-            int iw00, iw01, iw10, iw11;
-            bilin_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny), iw00, iw01, iw10, iw11);
-            if (!(jr_covers(inx, iny, w, h, jr_x0, jr_y0, JRW, JRH))) {
-                // every wave's JP reads of iteration j-1 precede that iteration's
-                // barrier, which this wave has passed
-                JPStage<NT> cp;
-                jr_x0 = (inx - kStJMargin) & ~3;
-                jr_y0 = iny - kStJMargin;
-                cp.copy(JP, J, jr_y0, jr_x0, JRW, JRH, wk_int, wk_bord);
-                __syncthreads();
-                PSN_PH_COUNT(acc_ph, 5);
-            }
-            const unsigned W0 = pack_w(iw00, iw01), W1 = pack_w(iw10, iw11);
-            const uint32_t *jb = JP + (iny - jr_y0) * JRW + (inx - jr_x0);
-            float *pb = R + (j & 1) * 2 * GB.P;
-            int s1 = 0, s2 = 0;
-            unsigned a = 0;
-#pragma unroll
-            for (int k = 0; k < EPT; k++) {
-                const uint32_t *p = jb + ofsJ[k];
-                const int jv = sdot2(p[JRW], W1, sdot2(p[0], W0, 1 << 8)) >> 9;
-                const int diff = jv - Iw_[k];
-                const int t1 = __mul24(diff, Ix_[k]), t2 = __mul24(diff, Iy_[k]);
-                pb[posB_[k]] = (float)t1;
-                pb[GB.P + posB_[k]] = (float)t2;
-                s1 += t1;
-                s2 += t2;
-                a += (unsigned)__mul24(abs(diff), (int)Sxy[k]);  // |t1| + |t2| (both factors < 2^14); per thread < 2^30
-            }
-            PSN_PH_MARK(acc_ph, t_ph, 0);
-            block_sums3<NT>(s1, s2, a, RI + kStRiIt + 32 * (j & 1));  // the iteration's barrier
-            PSN_PH_MARK(acc_ph, t_ph, 1);
-            float b1, b2;
-            if (a <= (unsigned)kExact) {
-                b1 = (float)s1;
-                b2 = (float)s2;
-            } else {
-                float acc = 0.f;
-                if (lane < 10) {
-                    const int ch = lane % 5, s = lane / 5;
-                    const int base = s * GB.P + (ch < 4 ? ch * GB.S : 4 * GB.S);
-                    const int nb = (ch < 4 ? GB.S : GB.T) >> 4;
-                    acc = chain_sum16(pb + base, nb);
+        // ---- multi-wave iterations: the windows with more than kOwMaxRows rows per
+        // lane of the one-wave geometry (40x20, 33x31, 20x50, every w > 64), a
+        // one-wave plan past the LDS cap, and the forced workgroup sizes. Every wave
+        // owns EPT pixels per thread; one workgroup barrier per iteration. ----
+        for (int level = maxL; level >= 0; level--) {
+            LK_STAMP(level * 10 + 0);
+            const LevelDev I = tbl_get(TBL, 0, level);
+            const LevelDev J = tbl_get(TBL, 1, level);
+            const int cols = I.w, rows = I.h;
+            const LevelStart ls =
+                level_start(level, maxL, flags, px0, py0, hwx, hwy, w, h, cols, rows, LV, NPx, NPy, status, errv);
+            const float *lv = ls.lv;
+            const bool run = ls.run;
+            float nx = ls.nx, ny = ls.ny;
+            if (run) {
+                // this level's J region: the prefetched registers if they cover the start
+                const int inx0 = cv_floor(nx), iny0 = cv_floor(ny);
+                if (pf_level == level && jr_covers(inx0, iny0, w, h, pfo.x0, pfo.y0, JRW, JRH)) {
+                    pf.store(JP);
+                    jr = pfo;
+                } else {
+                    jr = jr_origin(inx0, iny0, false);
+                    jr_restage<NT>(JP, J, jr, JRW, JRH, 0, wk_int, wk_bord, false);
                 }
-                combine_b10([&](int i) { return readlane_f(acc, i); }, sse, b1, b2);
-                PSN_PH_COUNT(acc_ph, 4);
             }
-            PSN_PH_MARK(acc_ph, t_ph, 2);
-            float dx, dy;
-            const double dd = lk_update(A11, A12, A22, D, b1, b2, hwx, hwy, nx, ny, NPx, NPy, dx, dy);
-            PSN_PH_MARK(acc_ph, t_ph, 3);
-            if (lk_stop(dd, Q.eps2, j, dx, dy, pdx, pdy, NPx, NPy)) break;
-        }
-        LK_STAMP(level * 10 + 7);
-        LK_COUNT(level * 10 + 8, jdone);
-        (void)jdone;
+            pf_level = -1;
+            if (level > 0) {  // prefetch the next level's region where this level's start predicts it
+                const Guess gn = level_guess(level - 1, maxL, flags, px0, py0, NPx, NPy);
+                pfo = jr_origin(cv_floor(__fsub_rn(gn.x, hwx)), cv_floor(__fsub_rn(gn.y, hwy)), false);
+                pf_level = level - 1;
+                pf.load(tbl_get(TBL, 1, level - 1), pfo.y0, pfo.x0, JRW, JRH, wk_int, wk_bord);
+            }
+            if (!run) continue;
+            __syncthreads();  // JP published (every wave finished the previous level's reads)
+            LK_STAMP(level * 10 + 1);
 
-        if (level == 0 && status && A.err && (flags & PSN_LK_GET_MIN_EIGENVALS) == 0) {
-            const float qx = __fsub_rn(NPx, hwx), qy = __fsub_rn(NPy, hwy);
-            const int iqx = cv_floor(qx), iqy = cv_floor(qy);
-            if (win_outside(iqx, iqy, w, h, cols, rows)) {
-                status = 0;
-                continue;
-            }
-            if (flags & PSN_LK_ERR_STATUS_ONLY) continue;  // the re-check was all: err[] = 0
-            int iw00, iw01, iw10, iw11;
-            bilin_weights(__fsub_rn(qx, (float)iqx), __fsub_rn(qy, (float)iqy), iw00, iw01, iw10, iw11);
-            __syncthreads();  // every wave is done with R (last products) and JP
-            if (!(jr_covers(iqx, iqy, w, h, jr_x0, jr_y0, JRW, JRH))) {
-                JPStage<NT> cp;
-                jr_x0 = (iqx - kStJMargin) & ~3;
-                jr_y0 = iqy - kStJMargin;
-                cp.copy(JP, J, jr_y0, jr_x0, JRW, JRH, wk_int, wk_bord);
-                __syncthreads();
-            }
-            const unsigned W0 = pack_w(iw00, iw01), W1 = pack_w(iw10, iw11);
-            const uint32_t *jb = JP + (iqy - jr_y0) * JRW + (iqx - jr_x0);
-            int e1 = 0, e2 = 0;
-            unsigned ea = 0;
+            const float A11 = lv[0], A12 = lv[1], A22 = lv[2], D = lv[3];
+            int Iw_[EPT], Ix_[EPT], Iy_[EPT];
+            unsigned Sxy[EPT];
+            {
+                const int2 *IW = (const int2 *)(smem + lay.iw + level * lay.iw_stride);
 #pragma unroll
-            for (int k = 0; k < EPT; k++) {
-                const uint32_t *p = jb + ofsJ[k];
-                const int jv = sdot2(p[JRW], W1, sdot2(p[0], W0, 1 << 8)) >> 9;
-                const int ad = ev[k] ? abs(jv - Iw_[k]) : 0;
-                R[ofsE[k]] = (float)ad;  // row-major, for the sequential fallback
-                ea += (unsigned)ad;
+                for (int k = 0; k < EPT; k++) {
+                    const int2 t = IW[pix[k]];
+                    Iw_[k] = t.x;
+                    Ix_[k] = ev[k] ? (int)(short)(t.y & 0xffff) : 0;
+                    Iy_[k] = ev[k] ? (t.y >> 16) : 0;
+                    Sxy[k] = (unsigned)(abs(Ix_[k]) + abs(Iy_[k]));
+                }
             }
-            for (int k = wh + tid; k < round16i(wh); k += NT) R[k] = 0.f;
-            block_sums3<NT>(e1, e2, ea, RI + kStRiErr);
-            float errval;
-            if (ea <= (unsigned)kExact) {
-                errval = (float)ea;  // every partial sum of errval += |diff| is an exact integer
-            } else {
-                float acc = 0.f;
-                if (lane == 0) acc = chain_sum16(R, round16i(wh) >> 4);
-                errval = readlane_f(acc, 0);
+            LK_STAMP(level * 10 + 2);
+            float pdx = 0.f, pdy = 0.f;
+            int jdone = 0;
+
+            for (int j = 0; j < Q.max_count; j++) {
+                jdone = j + 1;
+                PSN_CLK_ORDERED(t_ph);
+                const int inx = cv_floor(nx), iny = cv_floor(ny);
+                if (win_outside(inx, iny, w, h, cols, rows)) {
+                    if (level == 0) status = 0;
+                    break;
+                }
+                int iw00, iw01, iw10, iw11;
+                bilin_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny), iw00, iw01, iw10, iw11);
+                if (!(jr_covers(inx, iny, w, h, jr.x0, jr.y0, JRW, JRH))) {
+                    // every wave's JP reads of iteration j-1 precede that iteration's
+                    // barrier, which this wave has passed
+                    jr = jr_origin(inx, iny, false);
+                    jr_restage<NT>(JP, J, jr, JRW, JRH, 0, wk_int, wk_bord, false);
+                    __syncthreads();
+                    PSN_PH_COUNT(acc_ph, 5);
+                }
+                const unsigned W0 = pack_w(iw00, iw01), W1 = pack_w(iw10, iw11);
+                const uint32_t *jb = JP + (iny - jr.y0) * JRW + (inx - jr.x0);
+                float *pb = R + (j & 1) * 2 * GB.P;
+                int s1 = 0, s2 = 0;
+                unsigned a = 0;
+#pragma unroll
+                for (int k = 0; k < EPT; k++) {
+                    const uint32_t *p = jb + ofsJ[k];
+                    const int jv = sdot2(p[JRW], W1, sdot2(p[0], W0, 1 << 8)) >> 9;
+                    const int diff = jv - Iw_[k];
+                    const int t1 = __mul24(diff, Ix_[k]), t2 = __mul24(diff, Iy_[k]);
+                    pb[posB_[k]] = (float)t1;
+                    pb[GB.P + posB_[k]] = (float)t2;
+                    s1 += t1;
+                    s2 += t2;
+                    // |t1| + |t2| (both factors < 2^14); per thread < 2^30
+                    a += (unsigned)__mul24(abs(diff), (int)Sxy[k]);
+                }
+                PSN_PH_MARK(acc_ph, t_ph, 0);
+                block_sums3<NT>(s1, s2, a, RI + kStRiIt + 32 * (j & 1));  // the iteration's barrier
+                PSN_PH_MARK(acc_ph, t_ph, 1);
+                float b1, b2;
+                if (a <= (unsigned)kExact) {
+                    b1 = (float)s1;
+                    b2 = (float)s2;
+                } else {
+                    b_chains(pb, GB, sse, lane, b1, b2);  // every wave for itself: no second barrier
+                    PSN_PH_COUNT(acc_ph, 4);
+                }
+                PSN_PH_MARK(acc_ph, t_ph, 2);
+                float dx, dy;
+                const double dd = lk_update(A11, A12, A22, D, b1, b2, hwx, hwy, nx, ny, NPx, NPy, dx, dy);
+                PSN_PH_MARK(acc_ph, t_ph, 3);
+                if (lk_stop(dd, Q.eps2, j, dx, dy, pdx, pdy, NPx, NPy)) break;
             }
-            errv = lk_err(errval, wh);
+            LK_STAMP(level * 10 + 7);
+            LK_COUNT(level * 10 + 8, jdone);
+            (void)jdone;
+
+            if (level == 0 && status && A.err && (flags & PSN_LK_GET_MIN_EIGENVALS) == 0) {
+                const float qx = __fsub_rn(NPx, hwx), qy = __fsub_rn(NPy, hwy);
+                const int iqx = cv_floor(qx), iqy = cv_floor(qy);
+                if (win_outside(iqx, iqy, w, h, cols, rows)) {
+                    status = 0;
+                    continue;
+                }
+                if (flags & PSN_LK_ERR_STATUS_ONLY) continue;  // the re-check was all: err[] = 0
+                int iw00, iw01, iw10, iw11;
+                bilin_weights(__fsub_rn(qx, (float)iqx), __fsub_rn(qy, (float)iqy), iw00, iw01, iw10, iw11);
+                __syncthreads();  // every wave is done with JP
+                if (!(jr_covers(iqx, iqy, w, h, jr.x0, jr.y0, JRW, JRH))) {
+                    jr = jr_origin(iqx, iqy, false);
+                    jr_restage<NT>(JP, J, jr, JRW, JRH, 0, wk_int, wk_bord, false);
+                    __syncthreads();
+                }
+                const unsigned W0 = pack_w(iw00, iw01), W1 = pack_w(iw10, iw11);
+                const uint32_t *jb = JP + (iqy - jr.y0) * JRW + (iqx - jr.x0);
+                int e1 = 0, e2 = 0;
+                unsigned ea = 0;
+#pragma unroll
+                for (int k = 0; k < EPT; k++) {
+                    const uint32_t *p = jb + ofsJ[k];
+                    const int jv = sdot2(p[JRW], W1, sdot2(p[0], W0, 1 << 8)) >> 9;
+                    ea += (unsigned)(ev[k] ? abs(jv - Iw_[k]) : 0);
+                }
+                block_sums3<NT>(e1, e2, ea, RI + kStRiErr);
+                // ea <= kStErrSumMax <= kExact (psn_lk_kernels.h): every partial sum of
+                // errval += |diff|, in any order, is an exact integer
+                const float errval = (float)ea;
+                errv = lk_err(errval, wh);
+            }
         }
-    }
-    }  // legacy multi-wave iterations
+    }  // multi-wave iterations
 
     LK_STAMP(61);
     for (int i = 0; i < 8; i++) LK_COUNT(40 + i, acc_ph[i]);
