@@ -22,6 +22,11 @@
 // (and, in the A phase, one row band of the I patch and its Scharr plane), so
 // several workgroups share a CU and hide each other's serial chains.
 //
+// One helper per phase beside the kernel: lg_slot_index (the slot layout), lg_walk
+// (A runs, main pass, err pass), lg_runs_exact (run records -> block check),
+// lg_tiles / lg_store_quad / lg_ordered (ordered chains -> uniform result); the
+// level's guess is level_guess (psn_lk_solve.h); instantiations: PSN_LG_KERNELS.
+//
 // Bit-identical to oracle/lk_oracle.c (the SSE2 build's summation order, or the
 // scalar build's with PSN_LK_ACCUM_SCALAR).
 #include "psn_lk_bx.h"
@@ -63,14 +68,49 @@ __device__ __forceinline__ LgGeo lg_geo(int w, int h, bool sse) {
     g.rK = __fdiv_rn(1.f, (float)g.K);
     return g;
 }
+// row y and quad column qx of quad q
+struct LgRC {
+    int y, qx;
+};
+__device__ __forceinline__ LgRC lg_rc(const LgGeo &g, int q) {
+    const int y = lg_div(q, g.QW, g.rQW);
+    return {y, q - y * g.QW};
+}
 // terms of the SSE chains (one per SSE quad) and of the tail chain before quad q
 __device__ __forceinline__ int lg_sse_before(const LgGeo &g, int q, int nS) {
-    const int y = lg_div(q, g.QW, g.rQW);
-    return y * nS + min(q - y * g.QW, nS);
+    const LgRC r = lg_rc(g, q);
+    return r.y * nS + min(r.qx, nS);
 }
 __device__ __forceinline__ int lg_tail_before(const LgGeo &g, int q, int nS, int t) {
-    const int y = lg_div(q, g.QW, g.rQW);
-    return y * t + min(max(4 * (q - y * g.QW - nS), 0), t);
+    const LgRC r = lg_rc(g, q);
+    return r.y * t + min(max(4 * (r.qx - nS), 0), t);
+}
+
+// The workgroup's HBM slot: the window values of every quad, three planes (I*,
+// Ix*, Iy*; 4 pixels as packed 16-bit pairs) laid out [j][t]: quad q = t * K + j
+// (thread t's j-th) at j * NT + t, so the j-th quads of a wave are one coalesced load.
+struct LgSlot {
+    uint2 *ip, *xp, *yp;
+};
+__device__ __forceinline__ int lg_slot_index(const LgGeo &g, int q) {
+    const int t = lg_div(q, g.K, g.rK);
+    return (q - t * g.K) * kLgNT + t;
+}
+// One quad's window values; a pass loads the planes it reads (LI, LX, LY).
+struct LgQ {
+    uint2 ip, xp, yp;
+};
+template <bool LI, bool LX, bool LY>
+__device__ __forceinline__ LgQ lg_load(const LgSlot &S, int idx) {
+    LgQ v{};
+    if constexpr (LI) v.ip = S.ip[idx];
+    if constexpr (LX) v.xp = S.xp[idx];
+    if constexpr (LY) v.yp = S.yp[idx];
+    return v;
+}
+// the 4 pixels of a packed plane value
+__device__ __forceinline__ void lg_unpack4(const uint2 &p, int (&v)[4]) {
+    v[0] = lo16(p.x), v[1] = hi16(p.x), v[2] = lo16(p.y), v[3] = hi16(p.y);
 }
 
 // One quad's J - I* (4 pixels) at window row y, quad column qx: from the LDS copy
@@ -120,7 +160,8 @@ __device__ __forceinline__ LgJ lg_j(const LevelDev &J, int inx, int iny, int w, 
 // calcOpticalFlowPyrLK: copyMakeBorder(..., BORDER_REFLECT_101)); the LDS copy
 // holds them already (dma_patch).
 __device__ __forceinline__ void lg_diffs(const LgJ &J, int y, int qx, const uint2 &ip, int (&d)[4]) {
-    const int I[4] = {lo16(ip.x), hi16(ip.x), lo16(ip.y), hi16(ip.y)};
+    int I[4];
+    lg_unpack4(ip, I);
     if (J.lds || J.in) {
         uint32_t a0, a1, b0, b1;
         if (J.lds) {
@@ -155,11 +196,6 @@ __device__ __forceinline__ void lg_diffs(const LgJ &J, int y, int qx, const uint
 // LDS tile planes of the ordered-chain fallbacks (psn_lk_kernels.h): per plane 4
 // SSE chain regions of up to TQ terms and a tail region of up to 4*TQ terms
 // (16-float blocks + 4: conflict-free across the chain lanes' 16-B reads)
-
-// One quad's window values as the fallback writers hold them between tiles.
-struct LgQ {
-    uint2 ip, xp, yp;
-};
 
 // Ordered chains from quad qs on, tile by tile: waves 1-3 write a tile's products
 // (one quad per thread: `load(q)` fetches quad q's window values, `store(v, q,
@@ -236,11 +272,138 @@ __device__ __forceinline__ float lg_tiles(int qs, int NQ, float *buf, int nch, f
     return acc;
 }
 
+// The fallback tile writer (lg_tiles' `store`): quad q's terms of NPL sums into the
+// tile starting at quad a, planes at buf. Chains split at quad column nS: pixel i
+// of an SSE2 quad is a term of lane chain i, the pixels of the later quads are
+// tail chain terms in order (tT per row, cut at the window's width). term(i, t)
+// gives pixel i's NPL terms.
+template <int NPL, int TQ, typename Term>
+__device__ __forceinline__ void lg_store_quad(const LgGeo &G, int nS, int tT, int q, int qx, int a, float *buf,
+                                              Term term) {
+    constexpr int PLN = lg_plane(TQ), SR = lg_sreg(TQ);
+    auto put = [&](float *p, int i) {
+        float t[NPL];
+        term(i, t);
+#pragma unroll
+        for (int s = 0; s < NPL; s++) p[s * PLN] = t[s];
+    };
+    if (qx < nS) {
+        const int pos = lg_sse_before(G, q, nS) - lg_sse_before(G, a, nS);
+#pragma unroll
+        for (int i = 0; i < 4; i++) put(buf + i * SR + pos, i);
+    } else {
+        const int pos = lg_tail_before(G, q, nS, tT) - lg_tail_before(G, a, nS, tT);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (4 * qx + i >= G.w) break;
+            put(buf + 4 * SR + pos + i, i);
+        }
+    }
+}
+
+// Ordered chains to a uniform result: the 5 * NPL chains of NPL sums (3: A11,
+// A12, A22; 2: b1, b2) from quad qs on, chain lanes starting from `base`
+// (lg_tiles over the planes at PL); wave 0 combines its chain lanes in the SSE2
+// build's order and all threads read r[] back from RS[0 .. NPL) after one
+// barrier. The writers load the X and Y planes (and I with LI); terms(v, y, qx)
+// returns the per-pixel term callable of a quad (lg_store_quad). mark(0 .. 3) as
+// in lg_tiles, mark(4) once the tiles are summed.
+template <int NPL, int TQ, bool LI, typename Terms, typename Mark>
+__device__ __forceinline__ void lg_ordered(const LgGeo &G, int nS, int tT, const LgSlot &S, int qs, float base,
+                                           float *PL, float *RS, bool sse, Terms terms, Mark mark, float (&r)[NPL]) {
+    static_assert(NPL == 2 || NPL == 3, "b1, b2 or A11, A12, A22");
+    auto before = [&](int q, int &bs, int &bt) {
+        bs = lg_sse_before(G, q, nS);
+        bt = lg_tail_before(G, q, nS, tT);
+    };
+    auto load = [&](int q) { return lg_load<LI, true, true>(S, lg_slot_index(G, q)); };
+    auto store = [&](const LgQ &v, int q, int a, float *buf) {
+        const LgRC rc = lg_rc(G, q);
+        lg_store_quad<NPL, TQ>(G, nS, tT, q, rc.qx, a, buf, terms(v, rc.y, rc.qx));
+    };
+    const float acc = lg_tiles<NPL, TQ>(qs, G.NQ, PL, 5 * NPL, base, load, store, before, mark);
+    mark(4);
+    if (threadIdx.x < 64) {  // wave 0 combines in the SSE2 build's order
+        auto chain = [&](int i) { return readlane_f(acc, i); };
+        float t[NPL];
+        if constexpr (NPL == 3) {
+#pragma unroll
+            for (int s = 0; s < 3; s++) t[s] = combine_a5(chain, s, sse);
+        } else {
+            combine_b10(chain, sse, t[0], t[1]);
+        }
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int s = 0; s < NPL; s++) RS[s] = t[s];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < NPL; s++) r[s] = RS[s];
+}
+
+// The walk over a thread's quads [q0, q0 + cnt), q0 at row y0, quad column x0, in
+// order: body(v, y, qx) per quad with the planes LI / LX / LY of its window
+// values. Batches of kLgMB quads have their slot loads in flight together.
+constexpr int kLgMB = 4;
+template <bool LI, bool LX, bool LY, typename Body>
+__device__ __forceinline__ void lg_walk(const LgSlot &S, int cnt, int y0, int x0, int QW, Body body) {
+    const int tid = threadIdx.x;
+    int y = y0, qx = x0;
+    auto quad = [&](const LgQ &v) {
+        body(v, y, qx);
+        if (++qx == QW) {
+            qx = 0;
+            y++;
+        }
+    };
+    int k = 0;
+    for (; k + kLgMB <= cnt; k += kLgMB) {
+        // (one array per plane, not LgQ[kLgMB]: from an array of structs the compiler
+        // issues the loads plane-major and the third quad waits for the whole batch,
+        // s_waitcnt vmcnt 11, 7, 4, 0 in place of 11, 7, 6, 5, 3, 2, 0)
+        uint2 ip[kLgMB] = {}, xp[kLgMB] = {}, yp[kLgMB] = {};
+#pragma unroll
+        for (int u = 0; u < kLgMB; u++) {
+            const int ix = (k + u) * kLgNT + tid;
+            if constexpr (LI) ip[u] = S.ip[ix];
+            if constexpr (LX) xp[u] = S.xp[ix];
+            if constexpr (LY) yp[u] = S.yp[ix];
+        }
+#pragma unroll
+        for (int u = 0; u < kLgMB; u++) quad(LgQ{ip[u], xp[u], yp[u]});
+    }
+    for (; k < cnt; k++) quad(lg_load<LI, LX, LY>(S, k * kLgNT + tid));
+}
+
+// The block's exactness check of a thread's run records of N = 5 x sums chains
+// (chain 5 s + c: sum s, c 0-3 the SSE2 lanes, 4 the tail; T, M, m: total,
+// maximum and minimum prefix of the thread's contiguous run of each chain) by
+// bx_publish / bx_check_t / bx_eval_t on the records of parity par, two
+// barriers: true when every chain's float sum is its integer total (lane c:
+// tot), else the first failing thread h0 and, on lane c, chain c's exact prefix
+// base0 before that thread's run. bad: the thread's terms are not all exact
+// floats. T becomes the wave-exclusive prefix (bx_publish).
+template <int N>
+__device__ __forceinline__ bool lg_runs_exact(int (&T)[N], const int (&M)[N], const int (&m)[N], bool bad, int *X,
+                                              int &par, bool no_tail, int &tot, int &h0, int &base0) {
+    // a run whose own prefix leaves [-2^25, 2^25] cannot stay exact after any
+    // exact start (|start| <= 2^24): flag it (terms < 2^26 are seen before any
+    // wrap; the saturating A11 / A22 runs never wrap)
+#pragma unroll
+    for (int c = 0; c < N; c++) bad |= M[c] > (1 << 25) || m[c] < -(1 << 25);
+    int *rec = X + par * 4 * kBxRecInts;
+    par ^= 1;
+    bx_publish<N>(T, rec, no_tail);
+    __syncthreads();
+    bx_check_t<N>(T, M, m, bad, rec, no_tail);
+    __syncthreads();
+    return bx_eval_t<N>(rec, tot, h0, base0);
+}
+
 // Diagnostic phase clocks (PSN_LK_STAMPS build, psn_lk_stamps.h; tools/lg_stamps.py):
 // accumulated s_memtime ticks per phase of each point in lg_acc, thread 0's view,
 // written as stamps[point][0..23] at the end.
-
-constexpr int kLgMB = 4;  // quads per batch of slot loads in the passes over the window
 
 // TQ: quads per ordered-chain tile (kLgTQs; the planner's choice per query).
 // Minimum waves per SIMD 1: asking for more workgroups per CU was measured slower.
@@ -271,7 +434,10 @@ __global__ __launch_bounds__(kLgNT, 1) void lk_kernel_lg(LkLaunchArgs A) {
         const bool sse = (flags & PSN_LK_ACCUM_SCALAR) == 0;
         const LgGeo G = lg_geo(w, h, sse);
         const int K = G.K, QW = G.QW, NQ = G.NQ;
-        uint2 *IPs = (uint2 *)slot, *XPs = IPs + NT * K, *YPs = XPs + NT * K;
+        // (each plane from the one before: with all three as offsets of `slot` the A runs'
+        // batch waits for all its loads at once and the kernel takes 151 VGPRs, not 149)
+        uint2 *const IPs = (uint2 *)slot, *const XPs = IPs + NT * K;
+        const LgSlot SL = {IPs, XPs, XPs + NT * K};
         const int q0 = min(tid * K, NQ), cnt = min(NQ - q0, K);  // this thread's quads [q0, q0 + cnt)
         const int y0 = q0 / QW, x0 = q0 - y0 * QW;
         const int PM = bx_pm(w);  // I patch dwords per row
@@ -299,7 +465,6 @@ __global__ __launch_bounds__(kLgNT, 1) void lk_kernel_lg(LkLaunchArgs A) {
             const LevelDev I = ring_level_u(A.ring, Q.prev_slot, level);
             const LevelDev J = ring_level_u(A.ring, Q.next_slot, level);
             const int cols = I.w, rows = I.h;
-            const float scale = ldexpf(1.f, -level);
             // the LDS copy of the J region around the window (lg_jr): restaged when the
             // window at (inx, iny) leaves it (the A phase's bands and tiles reuse its LDS)
             bool jr_valid = false;
@@ -316,28 +481,13 @@ __global__ __launch_bounds__(kLgNT, 1) void lk_kernel_lg(LkLaunchArgs A) {
                 }
                 return lg_j(J, inx, iny, w, h, w00, w01, w10, w11, jrm ? JR : nullptr, JRP4, jr_x0, jr_y0);
             };
-            float px = __fmul_rn(px0, scale), py = __fmul_rn(py0, scale);
-            float nx, ny;
-            if (level == maxL) {
-                if (flags & PSN_LK_USE_INITIAL_FLOW) {
-                    nx = __fmul_rn(NPx, scale);
-                    ny = __fmul_rn(NPy, scale);
-                } else {
-                    nx = px;
-                    ny = py;
-                }
-            } else {
-                nx = __fmul_rn(NPx, 2.f);
-                ny = __fmul_rn(NPy, 2.f);
-            }
-            NPx = nx;
-            NPy = ny;
-            px = __fsub_rn(px, hwx);
-            py = __fsub_rn(py, hwy);
+            const Guess gs = level_guess(level, maxL, flags, px0, py0, NPx, NPy);
+            NPx = gs.x;
+            NPy = gs.y;
+            const float scale = ldexpf(1.f, -level);
+            const float px = __fsub_rn(__fmul_rn(px0, scale), hwx), py = __fsub_rn(__fmul_rn(py0, scale), hwy);
             const int ipx = cv_floor(px), ipy = cv_floor(py);
-            // (win_outside, written out at this kernel's three sites: through the helper the
-            // compiler folds the tests differently and the kernel's VGPR count changes)
-            if (ipx < -w || ipx >= cols || ipy < -h || ipy >= rows) {
+            if (win_outside(ipx, ipy, w, h, cols, rows)) {
                 if (level == 0) {
                     status = 0;
                     errv = 0.f;
@@ -346,8 +496,7 @@ __global__ __launch_bounds__(kLgNT, 1) void lk_kernel_lg(LkLaunchArgs A) {
             }
             int iw00, iw01, iw10, iw11;
             bilin_weights(__fsub_rn(px, (float)ipx), __fsub_rn(py, (float)ipy), iw00, iw01, iw10, iw11);
-            nx = __fsub_rn(nx, hwx);
-            ny = __fsub_rn(ny, hwy);
+            float nx = __fsub_rn(gs.x, hwx), ny = __fsub_rn(gs.y, hwy);
             nwin++;
 
             // ---- A phase (1): window values, band by band: the band's I patch rows
@@ -374,10 +523,10 @@ __global__ __launch_bounds__(kLgNT, 1) void lk_kernel_lg(LkLaunchArgs A) {
                             unsigned ip[2], xp[2], yp[2];
                             bx_unit<IN, false>(P32, PM, sh, wk.y, wk.x, true, w, ipx, ipy + r0, cols, rows, iw00, iw01,
                                                iw10, iw11, c256, c8192, ip, xp, yp, gdum0, gdum1);
-                            const int q = (r0 + wk.y) * QW + wk.x, t = lg_div(q, K, G.rK), idx = (q - t * K) * NT + t;
-                            IPs[idx] = make_uint2(ip[0], ip[1]);
-                            XPs[idx] = make_uint2(xp[0], xp[1]);
-                            YPs[idx] = make_uint2(yp[0], yp[1]);
+                            const int idx = lg_slot_index(G, (r0 + wk.y) * QW + wk.x);
+                            SL.ip[idx] = make_uint2(ip[0], ip[1]);
+                            SL.xp[idx] = make_uint2(xp[0], xp[1]);
+                            SL.yp[idx] = make_uint2(yp[0], yp[1]);
                         }
                         PSN_PH_MARK(lg_acc, lg_t, 9);  // band quads
                     }
@@ -395,122 +544,51 @@ __global__ __launch_bounds__(kLgNT, 1) void lk_kernel_lg(LkLaunchArgs A) {
             float s3[3];   // the raw A11, A12, A22 sums
             int gmax = 0;  // max |Ix|, |Iy| of the thread's pixels (exactness of the b terms)
             {
-                int T11[5] = {0, 0, 0, 0, 0}, T22[5] = {0, 0, 0, 0, 0}, T12[5] = {0, 0, 0, 0, 0};
-                int M12[5] = {0, 0, 0, 0, 0}, m12[5] = {0, 0, 0, 0, 0};
-                int qx = x0;
-                auto quad = [&](const uint2 &xp, const uint2 &yp) {
-                    const int gx[4] = {lo16(xp.x), hi16(xp.x), lo16(xp.y), hi16(xp.y)};
-                    const int gy[4] = {lo16(yp.x), hi16(yp.x), lo16(yp.y), hi16(yp.y)};
+                int T[15] = {}, M[15] = {}, m[15] = {};  // run records; chains 0-4: A11, 5-9: A12, 10-14: A22
+                lg_walk<false, true, true>(SL, cnt, y0, x0, QW, [&](const LgQ &v, int, int qx) {
+                    int gx[4], gy[4];
+                    lg_unpack4(v.xp, gx);
+                    lg_unpack4(v.yp, gy);
                     // (A11 / A22 runs saturate at 2^30: a long run never wraps; a run past 2^25
                     // fails the check below, as it must)
+                    auto term = [&](int c, int i) {
+                        T[c] = (int)sat_add((unsigned)T[c], (unsigned)(gx[i] * gx[i]));
+                        T[10 + c] = (int)sat_add((unsigned)T[10 + c], (unsigned)(gy[i] * gy[i]));
+                        run_add(T[5 + c], M[5 + c], m[5 + c], gx[i] * gy[i]);
+                    };
                     if (qx < G.nA) {  // SSE2 quad: pixel i feeds lane chain i
 #pragma unroll
-                        for (int i = 0; i < 4; i++) {
-                            T11[i] = (int)sat_add((unsigned)T11[i], (unsigned)(gx[i] * gx[i]));
-                            T22[i] = (int)sat_add((unsigned)T22[i], (unsigned)(gy[i] * gy[i]));
-                            run_add(T12[i], M12[i], m12[i], gx[i] * gy[i]);
-                        }
+                        for (int i = 0; i < 4; i++) term(i, i);
                     } else {  // the tail chain, in order (pixels past w carry zero gradients)
 #pragma unroll
-                        for (int i = 0; i < 4; i++) {
-                            T11[4] = (int)sat_add((unsigned)T11[4], (unsigned)(gx[i] * gx[i]));
-                            T22[4] = (int)sat_add((unsigned)T22[4], (unsigned)(gy[i] * gy[i]));
-                            run_add(T12[4], M12[4], m12[4], gx[i] * gy[i]);
-                        }
+                        for (int i = 0; i < 4; i++) term(4, i);
                     }
 #pragma unroll
                     for (int i = 0; i < 4; i++) gmax = max(gmax, max(abs(gx[i]), abs(gy[i])));
-                    if (++qx == QW) qx = 0;
-                };
-                int k = 0;
-                for (; k + kLgMB <= cnt; k += kLgMB) {
-                    uint2 xp[kLgMB], yp[kLgMB];
-#pragma unroll
-                    for (int u = 0; u < kLgMB; u++) {
-                        xp[u] = XPs[(k + u) * NT + tid];
-                        yp[u] = YPs[(k + u) * NT + tid];
-                    }
-#pragma unroll
-                    for (int u = 0; u < kLgMB; u++) quad(xp[u], yp[u]);
-                }
-                for (; k < cnt; k++) quad(XPs[k * NT + tid], YPs[k * NT + tid]);
+                });
                 // A11 / A22 terms are >= 0: the maximum prefix is the total
-                int T[15], M[15], m[15];
 #pragma unroll
-                for (int c = 0; c < 5; c++) {
-                    T[c] = T11[c], M[c] = T11[c], m[c] = 0;
-                    T[5 + c] = T12[c], M[5 + c] = M12[c], m[5 + c] = m12[c];
-                    T[10 + c] = T22[c], M[10 + c] = T22[c], m[10 + c] = 0;
-                }
-                // a run whose own prefix leaves [-2^25, 2^25] cannot stay exact after any
-                // exact start (|start| <= 2^24): flag it (long runs never wrap unseen)
-                bool badA = false;
-#pragma unroll
-                for (int c = 0; c < 15; c++) badA |= M[c] > (1 << 25) || m[c] < -(1 << 25);
-                int *rec = X + par * 4 * kBxRecInts;
-                par ^= 1;
-                bx_publish<15>(T, rec, G.tA == 0);
-                __syncthreads();
-                bx_check_t<15>(T, M, m, badA, rec, G.tA == 0);
-                __syncthreads();
+                for (int c = 0; c < 5; c++) M[c] = T[c], M[10 + c] = T[10 + c];
                 int tot, h0, base0;
-                const bool exact = bx_eval_t<15>(rec, tot, h0, base0);
-                if (exact) {
+                if (lg_runs_exact(T, M, m, false, X, par, G.tA == 0, tot, h0, base0)) {
 #pragma unroll
                     for (int s = 0; s < 3; s++) s3[s] = combine_a5([&](int i) { return rl_f(tot, i); }, s, sse);
                 } else {
                     // ordered chains from thread h0's run on (every earlier prefix is an
                     // exact integer: the chain lanes start from base0)
-                    const int qs = min(h0 * K, NQ);
-                    auto geoA = [&](int q, int &bs, int &bt) {
-                        bs = lg_sse_before(G, q, G.nA);
-                        bt = lg_tail_before(G, q, G.nA, G.tA);
-                    };
-                    auto loadA = [&](int q) {
-                        const int t = lg_div(q, K, G.rK), idx = (q - t * K) * NT + t;
-                        LgQ v;
-                        v.xp = XPs[idx];
-                        v.yp = YPs[idx];
-                        return v;
-                    };
-                    auto storeA = [&](const LgQ &v, int q, int a, float *buf) {
-                        const int gx[4] = {lo16(v.xp.x), hi16(v.xp.x), lo16(v.xp.y), hi16(v.xp.y)};
-                        const int gy[4] = {lo16(v.yp.x), hi16(v.yp.x), lo16(v.yp.y), hi16(v.yp.y)};
-                        const int PLA = lg_plane(TQ), SR = lg_sreg(TQ);
-                        const int y = lg_div(q, QW, G.rQW), qx = q - y * QW;
-                        if (qx < G.nA) {
-                            const int pos = lg_sse_before(G, q, G.nA) - lg_sse_before(G, a, G.nA);
-#pragma unroll
-                            for (int i = 0; i < 4; i++) {
-                                float *p = buf + i * SR + pos;
-                                p[0] = (float)(gx[i] * gx[i]);
-                                p[PLA] = (float)(gx[i] * gy[i]);
-                                p[2 * PLA] = (float)(gy[i] * gy[i]);
-                            }
-                        } else {
-                            const int pos = lg_tail_before(G, q, G.nA, G.tA) - lg_tail_before(G, a, G.nA, G.tA);
-#pragma unroll
-                            for (int i = 0; i < 4; i++) {
-                                if (4 * qx + i >= w) break;
-                                float *p = buf + 4 * SR + pos + i;
-                                p[0] = (float)(gx[i] * gx[i]);
-                                p[PLA] = (float)(gx[i] * gy[i]);
-                                p[2 * PLA] = (float)(gy[i] * gy[i]);
-                            }
-                        }
-                    };
-                    float acc = lg_tiles<3, TQ>(qs, NQ, PL, 15, (float)base0, loadA, storeA, geoA, [&](int) {});
-                    if (tid < 64) {  // wave 0 combines in the SSE2 build's order
-#pragma unroll
-                        for (int s = 0; s < 3; s++) {
-                            const float t = combine_a5([&](int i) { return readlane_f(acc, i); }, s, sse);
-                            if (tid == 0) RS[s] = t;
-                        }
-                    }
-                    __syncthreads();
-                    s3[0] = RS[0];
-                    s3[1] = RS[1];
-                    s3[2] = RS[2];
+                    lg_ordered<3, TQ, false>(
+                        G, G.nA, G.tA, SL, min(h0 * K, NQ), (float)base0, PL, RS, sse,
+                        [&](const LgQ &v, int, int) {
+                            int gx[4], gy[4];
+                            lg_unpack4(v.xp, gx);
+                            lg_unpack4(v.yp, gy);
+                            return [=](int i, float(&t)[3]) {
+                                t[0] = (float)(gx[i] * gx[i]);
+                                t[1] = (float)(gx[i] * gy[i]);
+                                t[2] = (float)(gy[i] * gy[i]);
+                            };
+                        },
+                        [&](int) {}, s3);
                 }
             }
             PSN_PH_MARK(lg_acc, lg_t, 1);  // A chains
@@ -524,7 +602,7 @@ __global__ __launch_bounds__(kLgNT, 1) void lk_kernel_lg(LkLaunchArgs A) {
             float pdx = 0.f, pdy = 0.f;
             for (int j = 0; j < Q.max_count; j++) {
                 const int inx = cv_floor(nx), iny = cv_floor(ny);
-                if (inx < -w || inx >= cols || iny < -h || iny >= rows) {
+                if (win_outside(inx, iny, w, h, cols, rows)) {
                     if (level == 0) status = 0;
                     break;
                 }
@@ -533,161 +611,75 @@ __global__ __launch_bounds__(kLgNT, 1) void lk_kernel_lg(LkLaunchArgs A) {
                 bilin_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny), w00, w01, w10, w11);
                 const LgJ JJ = window_j(inx, iny, w00, w01, w10, w11);
                 // ---- main pass: the thread's quads in order, the 10 b chains as runs ----
-                int T1[5] = {0, 0, 0, 0, 0}, M1[5] = {0, 0, 0, 0, 0}, m1[5] = {0, 0, 0, 0, 0};
-                int T2[5] = {0, 0, 0, 0, 0}, M2[5] = {0, 0, 0, 0, 0}, m2[5] = {0, 0, 0, 0, 0};
+                int T[10] = {}, M[10] = {}, m[10] = {};  // run records; chains 0-4: b1, 5-9: b2
                 int dmax = 0;
-                {
-                    int y = y0, qx = x0;
-                    auto quad = [&](const uint2 &ip, const uint2 &xp, const uint2 &yp) {
-                        int d[4];
-                        lg_diffs(JJ, y, qx, ip, d);
-                        const int gx[4] = {lo16(xp.x), hi16(xp.x), lo16(xp.y), hi16(xp.y)};
-                        const int gy[4] = {lo16(yp.x), hi16(yp.x), lo16(yp.y), hi16(yp.y)};
-                        if (qx < G.nB2) {  // SSE2 quad: pixel i feeds lane chain i
-#pragma unroll
-                            for (int i = 0; i < 4; i++) {
-                                run_add(T1[i], M1[i], m1[i], __mul24(d[i], gx[i]));
-                                run_add(T2[i], M2[i], m2[i], __mul24(d[i], gy[i]));
-                            }
-                        } else {  // the tail chain, in order (pixels past w: zero gradients)
-#pragma unroll
-                            for (int i = 0; i < 4; i++) {
-                                run_add(T1[4], M1[4], m1[4], __mul24(d[i], gx[i]));
-                                run_add(T2[4], M2[4], m2[4], __mul24(d[i], gy[i]));
-                            }
-                        }
-#pragma unroll
-                        for (int i = 0; i < 4; i++)
-                            if (4 * qx + i < w) dmax = max(dmax, abs(d[i]));
-                        if (++qx == QW) {
-                            qx = 0;
-                            y++;
-                        }
+                // a quad's diffs J - I* and gradients (the main pass and the fallback writers)
+                auto b_quad = [&](const LgQ &v, int y, int qx, int(&d)[4], int(&gx)[4], int(&gy)[4]) {
+                    lg_diffs(JJ, y, qx, v.ip, d);
+                    lg_unpack4(v.xp, gx);
+                    lg_unpack4(v.yp, gy);
+                };
+                lg_walk<true, true, true>(SL, cnt, y0, x0, QW, [&](const LgQ &v, int y, int qx) {
+                    int d[4], gx[4], gy[4];
+                    b_quad(v, y, qx, d, gx, gy);
+                    auto term = [&](int c, int i) {
+                        run_add(T[c], M[c], m[c], __mul24(d[i], gx[i]));
+                        run_add(T[5 + c], M[5 + c], m[5 + c], __mul24(d[i], gy[i]));
                     };
-                    // batches of kLgMB quads: their slot loads in flight together
-                    int k = 0;
-                    for (; k + kLgMB <= cnt; k += kLgMB) {
-                        uint2 ip[kLgMB], xp[kLgMB], yp[kLgMB];
+                    if (qx < G.nB2) {  // SSE2 quad: pixel i feeds lane chain i
 #pragma unroll
-                        for (int u = 0; u < kLgMB; u++) {
-                            const int ix = (k + u) * NT + tid;
-                            ip[u] = IPs[ix];
-                            xp[u] = XPs[ix];
-                            yp[u] = YPs[ix];
-                        }
+                        for (int i = 0; i < 4; i++) term(i, i);
+                    } else {  // the tail chain, in order (pixels past w: zero gradients)
 #pragma unroll
-                        for (int u = 0; u < kLgMB; u++) quad(ip[u], xp[u], yp[u]);
+                        for (int i = 0; i < 4; i++) term(4, i);
                     }
-                    for (; k < cnt; k++) {
-                        const int ix = k * NT + tid;
-                        quad(IPs[ix], XPs[ix], YPs[ix]);
-                    }
-                }
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        if (4 * qx + i < w) dmax = max(dmax, abs(d[i]));
+                });
                 PSN_PH_MARK(lg_acc, lg_t, 2);  // main pass
                 PSN_PH_COUNT(lg_acc, 10);
-                // every term is an exact float unless |d| * |g| > 2^24; a run past
-                // [-2^25, 2^25] (terms < 2^26: seen before any wrap) cannot be exact
-                bool bad = (long long)dmax * gmax > (long long)kExact;
-                int T[10], M[10], m[10];
-#pragma unroll
-                for (int c = 0; c < 5; c++) {
-                    T[c] = T1[c], M[c] = M1[c], m[c] = m1[c];
-                    T[5 + c] = T2[c], M[5 + c] = M2[c], m[5 + c] = m2[c];
-                }
-#pragma unroll
-                for (int c = 0; c < 10; c++) bad |= M[c] > (1 << 25) || m[c] < -(1 << 25);
-                int *rec = X + par * 4 * kBxRecInts;
-                par ^= 1;
-                bx_publish<10>(T, rec, G.tB == 0);
-                __syncthreads();
-                bx_check_t<10>(T, M, m, bad, rec, G.tB == 0);
-                __syncthreads();
+                // every term is an exact float unless |d| * |g| > 2^24
+                const bool bad = (long long)dmax * gmax > (long long)kExact;
                 int tot, h0, base0;
-                const bool bex = bx_eval_t<10>(rec, tot, h0, base0);
+                const bool bex = lg_runs_exact(T, M, m, bad, X, par, G.tB == 0, tot, h0, base0);
                 PSN_PH_MARK(lg_acc, lg_t, 3);  // publish / check / eval
-                float b1, b2;
+                float b[2];
                 if (bex) {
-                    combine_b10([&](int i) { return rl_f(tot, i); }, sse, b1, b2);
+                    combine_b10([&](int i) { return rl_f(tot, i); }, sse, b[0], b[1]);
                 } else {
                     PSN_PH_COUNT(lg_acc, 11);
+                    PSN_PH_MARK(lg_acc, lg_t, 4);
+                    // 18: pads of the next tile (14: tiles), 13: barrier wait, 16: writes, loads, tile
+                    // geometry, 17: chain sums, 5: ordered b chains
+                    auto markB = [&](int i) {
+                        PSN_PH_MARK(lg_acc, lg_t, i == 0 ? 18 : i == 1 ? 13 : i == 2 ? 16 : i == 3 ? 17 : 5);
+                        if (i == 0) PSN_PH_COUNT(lg_acc, 14);
+                    };
                     // ordered float chains from thread h0's run on (chain lanes: wave 0,
                     // lanes 0-9, from their exact prefixes base0), tiles of TQ quads
-                    const int qs = min(h0 * K, NQ);
-                    auto geoB = [&](int q, int &bs, int &bt) {
-                        bs = lg_sse_before(G, q, G.nB2);
-                        bt = lg_tail_before(G, q, G.nB2, G.tB);
-                    };
-                    auto loadB = [&](int q) {
-                        const int t = lg_div(q, K, G.rK), idx = (q - t * K) * NT + t;
-                        LgQ v;
-                        v.ip = IPs[idx];
-                        v.xp = XPs[idx];
-                        v.yp = YPs[idx];
-                        return v;
-                    };
-                    auto storeB = [&](const LgQ &v, int q, int a, float *buf) {
-                        const int y = lg_div(q, QW, G.rQW), qx = q - y * QW;
-                        int d[4];
-                        lg_diffs(JJ, y, qx, v.ip, d);
-                        const int gx[4] = {lo16(v.xp.x), hi16(v.xp.x), lo16(v.xp.y), hi16(v.xp.y)};
-                        const int gy[4] = {lo16(v.yp.x), hi16(v.yp.x), lo16(v.yp.y), hi16(v.yp.y)};
-                        const int PLB = lg_plane(TQ), SR = lg_sreg(TQ);
-                        if (qx < G.nB2) {
-                            const int pos = lg_sse_before(G, q, G.nB2) - lg_sse_before(G, a, G.nB2);
-#pragma unroll
-                            for (int i = 0; i < 4; i++) {
-                                float *p = buf + i * SR + pos;
-                                p[0] = (float)__mul24(d[i], gx[i]);
-                                p[PLB] = (float)__mul24(d[i], gy[i]);
-                            }
-                        } else {
-                            const int pos = lg_tail_before(G, q, G.nB2, G.tB) - lg_tail_before(G, a, G.nB2, G.tB);
-#pragma unroll
-                            for (int i = 0; i < 4; i++) {
-                                if (4 * qx + i >= w) break;
-                                float *p = buf + 4 * SR + pos + i;
-                                p[0] = (float)__mul24(d[i], gx[i]);
-                                p[PLB] = (float)__mul24(d[i], gy[i]);
-                            }
-                        }
-                    };
-                    PSN_PH_MARK(lg_acc, lg_t, 4);
-                    auto markB = [&](int i) {
-                        if (i == 0) {
-                            PSN_PH_MARK(lg_acc, lg_t, 18);  // ordered b chains: pads of the next tile
-                            PSN_PH_COUNT(lg_acc, 14);
-                        } else if (i == 1) {
-                            PSN_PH_MARK(lg_acc, lg_t, 13);  // barrier wait
-                        } else if (i == 2) {
-                            PSN_PH_MARK(lg_acc, lg_t, 16);  // writes, loads, tile geometry
-                        } else {
-                            PSN_PH_MARK(lg_acc, lg_t, 17);  // chain sums
-                        }
-                    };
-                    const float acc = lg_tiles<2, TQ>(qs, NQ, PL, 10, (float)base0, loadB, storeB, geoB, markB);
-                    PSN_PH_MARK(lg_acc, lg_t, 5);  // ordered b chains
-                    if (tid < 64) {  // wave 0 combines in the SSE2 build's order
-                        float r1, r2;
-                        combine_b10([&](int i) { return readlane_f(acc, i); }, sse, r1, r2);
-                        if (tid == 0) {
-                            RS[4] = r1;
-                            RS[5] = r2;
-                        }
-                    }
-                    __syncthreads();
-                    b1 = RS[4];
-                    b2 = RS[5];
+                    lg_ordered<2, TQ, true>(
+                        G, G.nB2, G.tB, SL, min(h0 * K, NQ), (float)base0, PL, RS + 4, sse,
+                        [&](const LgQ &v, int y, int qx) {
+                            int d[4], gx[4], gy[4];
+                            b_quad(v, y, qx, d, gx, gy);
+                            return [=](int i, float(&t)[2]) {
+                                t[0] = (float)__mul24(d[i], gx[i]);
+                                t[1] = (float)__mul24(d[i], gy[i]);
+                            };
+                        },
+                        markB, b);
                 }
                 PSN_PH_MARK(lg_acc, lg_t, 6);  // results
                 float dx, dy;
-                const double dd = lk_update(S.A11, S.A12, S.A22, S.invD, b1, b2, hwx, hwy, nx, ny, NPx, NPy, dx, dy);
+                const double dd = lk_update(S.A11, S.A12, S.A22, S.invD, b[0], b[1], hwx, hwy, nx, ny, NPx, NPy, dx, dy);
                 if (lk_stop(dd, Q.eps2, j, dx, dy, pdx, pdy, NPx, NPy)) break;
             }
 
             if (level == 0 && status && A.err && (flags & PSN_LK_GET_MIN_EIGENVALS) == 0) {
                 const float qxf = __fsub_rn(NPx, hwx), qyf = __fsub_rn(NPy, hwy);
                 const int iqx = cv_floor(qxf), iqy = cv_floor(qyf);
-                if (iqx < -w || iqx >= cols || iqy < -h || iqy >= rows) {
+                if (win_outside(iqx, iqy, w, h, cols, rows)) {
                     status = 0;
                     continue;
                 }
@@ -696,29 +688,13 @@ __global__ __launch_bounds__(kLgNT, 1) void lk_kernel_lg(LkLaunchArgs A) {
                 bilin_weights(__fsub_rn(qxf, (float)iqx), __fsub_rn(qyf, (float)iqy), w00, w01, w10, w11);
                 const LgJ JJ = window_j(iqx, iqy, w00, w01, w10, w11);
                 unsigned e = 0;
-                {
-                    int y = y0, qx = x0;
-                    auto quad = [&](const uint2 &ip) {
-                        int d[4];
-                        lg_diffs(JJ, y, qx, ip, d);
+                lg_walk<true, false, false>(SL, cnt, y0, x0, QW, [&](const LgQ &v, int y, int qx) {
+                    int d[4];
+                    lg_diffs(JJ, y, qx, v.ip, d);
 #pragma unroll
-                        for (int i = 0; i < 4; i++)
-                            if (4 * qx + i < w) e = sat_add(e, (unsigned)abs(d[i]));
-                        if (++qx == QW) {
-                            qx = 0;
-                            y++;
-                        }
-                    };
-                    int k = 0;
-                    for (; k + kLgMB <= cnt; k += kLgMB) {
-                        uint2 ip[kLgMB];
-#pragma unroll
-                        for (int u = 0; u < kLgMB; u++) ip[u] = IPs[(k + u) * NT + tid];
-#pragma unroll
-                        for (int u = 0; u < kLgMB; u++) quad(ip[u]);
-                    }
-                    for (; k < cnt; k++) quad(IPs[k * NT + tid]);
-                }
+                    for (int i = 0; i < 4; i++)
+                        if (4 * qx + i < w) e = sat_add(e, (unsigned)abs(d[i]));
+                });
                 e = wave_sum_sat(e);
                 if (lane == 0) EP[tid >> 6] = (int)e;
                 __syncthreads();
@@ -728,22 +704,25 @@ __global__ __launch_bounds__(kLgNT, 1) void lk_kernel_lg(LkLaunchArgs A) {
                     errval = (float)et;  // every partial sum of errval += |diff| is an exact integer
                 } else {  // row-major order, one lane, tiles of kLgTQE quads
                     float acc = 0.f;
+                    auto pixel_of = [&](int q) {  // row-major pixel index of quad q
+                        const LgRC rc = lg_rc(G, q);
+                        return rc.y * w + 4 * rc.qx;
+                    };
                     for (int a = 0; a < NQ; a += kLgTQE) {
                         const int b = min(a + kLgTQE, NQ);
-                        const int pa = lg_div(a, QW, G.rQW) * w + 4 * (a - lg_div(a, QW, G.rQW) * QW);  // row-major pixel index of quad a
+                        const int pa = pixel_of(a);
                         __syncthreads();
                         const int q = a + tid;
                         if (q < b) {
-                            const int t = lg_div(q, K, G.rK), idx = (q - t * K) * NT + t;
-                            const int y = lg_div(q, QW, G.rQW), qx = q - y * QW;
+                            const LgRC rc = lg_rc(G, q);
                             int d[4];
-                            lg_diffs(JJ, y, qx, IPs[idx], d);
+                            lg_diffs(JJ, rc.y, rc.qx, SL.ip[lg_slot_index(G, q)], d);
 #pragma unroll
                             for (int i = 0; i < 4; i++)
-                                if (4 * qx + i < w) PL[y * w + 4 * qx + i - pa] = (float)abs(d[i]);
+                                if (4 * rc.qx + i < w) PL[rc.y * w + 4 * rc.qx + i - pa] = (float)abs(d[i]);
                         }
                         __syncthreads();
-                        const int pb = b < NQ ? lg_div(b, QW, G.rQW) * w + 4 * (b - lg_div(b, QW, G.rQW) * QW) : w * h;
+                        const int pb = b < NQ ? pixel_of(b) : w * h;
                         if (tid == 0) acc = chain_sum(PL, pb - pa, acc);
                     }
                     if (tid == 0) RS[8] = acc;
@@ -774,21 +753,41 @@ __global__ __launch_bounds__(kLgNT, 1) void lk_kernel_lg(LkLaunchArgs A) {
     }
 }
 
+// The instantiations of lk_kernel_lg, written ONCE: the launch dispatch and the
+// dynamic-LDS attribute loop of lg_kernels_init are both generated from this
+// list, so a tile size cannot launch without its attribute. X(TQ): the
+// planner's tile sizes kLgTQs, in its order.
+#define PSN_LG_KERNELS(X) X(192) X(128)
+constexpr bool lg_kernels_are_tqs() {
+#define PSN_LG_TQ(TQ) TQ,
+    constexpr int tqs[] = {PSN_LG_KERNELS(PSN_LG_TQ)};
+#undef PSN_LG_TQ
+    if (sizeof(tqs) != sizeof(kLgTQs)) return false;
+    for (size_t i = 0; i < sizeof(tqs) / sizeof(tqs[0]); i++)
+        if (tqs[i] != kLgTQs[i]) return false;
+    return true;
+}
+static_assert(lg_kernels_are_tqs(), "PSN_LG_KERNELS must list exactly kLgTQs");
+
 hipError_t launch_lk_lg(const LkLaunchArgs &a, int grid, int lds_bytes, int tq, hipStream_t s) {
     if (grid <= 0 || a.lk_wgs <= 0) return hipSuccess;
-    if (!a.lg_ws || a.lg_slot <= 0 || lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-    switch (tq) {
-        case 192: hipLaunchKernelGGL(lk_kernel_lg<192>, dim3(grid), dim3(kLgNT), lds_bytes, s, a); break;
-        case 128: hipLaunchKernelGGL(lk_kernel_lg<128>, dim3(grid), dim3(kLgNT), lds_bytes, s, a); break;
-        default: return hipErrorInvalidValue;
+    if (!a.lg_ws || a.lg_slot <= 0 || lds_bytes > kMaxLdsBytes) return hipErrorInvalidValue;
+#define PSN_LG_LAUNCH(TQ)                                                                   \
+    if (tq == TQ) {                                                                         \
+        hipLaunchKernelGGL(lk_kernel_lg<TQ>, dim3(grid), dim3(kLgNT), lds_bytes, s, a);     \
+        return hipGetLastError();                                                           \
     }
-    return hipGetLastError();
+    PSN_LG_KERNELS(PSN_LG_LAUNCH)
+#undef PSN_LG_LAUNCH
+    return hipErrorInvalidValue;  // (a missing instantiation is an error, never another kernel)
 }
 
 hipError_t lg_kernels_init() {
-    const void *f[2] = {(const void *)lk_kernel_lg<192>, (const void *)lk_kernel_lg<128>};
-    for (const void *k : f) {
-        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+#define PSN_LG_FN(TQ) (const void *)lk_kernel_lg<TQ>,
+    const void *fns[] = {PSN_LG_KERNELS(PSN_LG_FN)};
+#undef PSN_LG_FN
+    for (const void *f : fns) {
+        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

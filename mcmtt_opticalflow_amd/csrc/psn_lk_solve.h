@@ -34,6 +34,29 @@ __device__ __forceinline__ bool jr_covers(int ix, int iy, int w, int h, int jr_x
     return ix >= jr_x0 && iy >= jr_y0 && ix + w + 1 <= jr_x0 + JRW && iy + h + 1 <= jr_y0 + JRH;
 }
 
+// The guess a level starts from: at the coarsest level the initial flow (or the
+// previous point) scaled to it, below it twice the level above's result.
+struct Guess {
+    float x, y;
+};
+__device__ __forceinline__ Guess level_guess(int level, int maxL, int flags, float px0, float py0, float NPx, float NPy) {
+    Guess gs;
+    const float scale = ldexpf(1.f, -level);
+    if (level == maxL) {
+        if (flags & PSN_LK_USE_INITIAL_FLOW) {
+            gs.x = __fmul_rn(NPx, scale);
+            gs.y = __fmul_rn(NPy, scale);
+        } else {
+            gs.x = __fmul_rn(px0, scale);
+            gs.y = __fmul_rn(py0, scale);
+        }
+    } else {
+        gs.x = __fmul_rn(NPx, 2.f);
+        gs.y = __fmul_rn(NPy, 2.f);
+    }
+    return gs;
+}
+
 // SSE2-order combination of the 5 ordered chain sums of A sum s (chains
 // 5s..5s+3 the lanes of the __m128 accumulator, 5s+4 the scalar tail):
 // tail + (((q0 + q1) + q2) + q3); the scalar build has the tail chain only.

@@ -450,29 +450,6 @@ __device__ __forceinline__ void b_chains(const float *pb, const ChainGeo &GB, bo
     combine_b10([&](int i) { return readlane_f(acc, i); }, sse, b1, b2);
 }
 
-// The guess a level starts from: at the coarsest level the initial flow (or the
-// previous point) scaled to it, below it twice the level above's result.
-struct Guess {
-    float x, y;
-};
-__device__ __forceinline__ Guess level_guess(int level, int maxL, int flags, float px0, float py0, float NPx, float NPy) {
-    Guess gs;
-    const float scale = ldexpf(1.f, -level);
-    if (level == maxL) {
-        if (flags & PSN_LK_USE_INITIAL_FLOW) {
-            gs.x = __fmul_rn(NPx, scale);
-            gs.y = __fmul_rn(NPy, scale);
-        } else {
-            gs.x = __fmul_rn(px0, scale);
-            gs.y = __fmul_rn(py0, scale);
-        }
-    } else {
-        gs.x = __fmul_rn(NPx, 2.f);
-        gs.y = __fmul_rn(NPy, 2.f);
-    }
-    return gs;
-}
-
 // Start of a level: NP becomes the level's guess; the level's solver row lv; run
 // = the I window is inside the image and the system is solvable; status and err
 // of a level that does not run (they count at level 0 only); the J window's

@@ -23,6 +23,8 @@ import functools
 import numpy as np
 import pytest
 
+from lk_window_sums import lane_sums as _lane_sums
+from lk_window_sums import window_grads as _window_grads
 from mcmtt_opticalflow_amd import _lib
 from mcmtt_opticalflow_amd import lk as glk
 from mcmtt_opticalflow_amd import synth
@@ -119,38 +121,6 @@ def _check(oracle_mod, kind, win, flags=0, **env):
     _same_bits(bx, ref, f"{kind} {win} flags {flags} {env} lk_kernel_bx vs oracle")
     _same_bits(fw, bx, f"{kind} {win} flags {flags} {env} forward entry vs lk_kernel_bx")
     return ref
-
-
-def _window_grads(oracle_mod, img, x, y, win):
-    """(gx, gy) of the window at point (x, y): the oracle's Scharr gradients with the
-    window's 14-bit bilinear weights, edge-padded; None when the window is outside."""
-    w, h = win
-    pad = max(w, h) + 32
-    g = np.pad(oracle_mod.scharr(img).astype(np.int64), ((pad, pad), (pad, pad), (0, 0)), mode="edge")
-    px = np.float32(x) - np.float32((w - 1) * 0.5)
-    py = np.float32(y) - np.float32((h - 1) * 0.5)
-    ix, iy = int(np.floor(px)), int(np.floor(py))
-    if ix < -w or iy < -h or ix > W or iy > H:
-        return None
-    a, b = float(px - np.float32(ix)), float(py - np.float32(iy))
-    w00, w01, w10 = round((1 - a) * (1 - b) * 16384), round(a * (1 - b) * 16384), round((1 - a) * b * 16384)
-    w11 = 16384 - w00 - w01 - w10
-    r = g[iy + pad:iy + pad + h + 1, ix + pad:ix + pad + w + 1]
-    v = (r[:-1, :-1] * w00 + r[:-1, 1:] * w01 + r[1:, :-1] * w10 + r[1:, 1:] * w11 + 8192) >> 14
-    return v[..., 0], v[..., 1]
-
-
-def _lane_sums(oracle_mod, img, pts, win):
-    """Per point the largest per-lane (x & 3) sum of Ix^2, of Iy^2 and of |Ix Iy| over
-    the level-0 window."""
-    out = []
-    for x, y in pts:
-        gr = _window_grads(oracle_mod, img, x, y, win)
-        if gr is None:
-            continue
-        gx, gy = gr
-        out.append([max(int(t[:, l::4].sum()) for l in range(4)) for t in (gx * gx, gy * gy, np.abs(gx * gy))])
-    return np.array(out, np.int64)
 
 
 def _bilinear(img, x0, y0, w, h):
